@@ -2,9 +2,15 @@
 """Benchmark of the MSM / NTT hot path (BASELINE.json metric: "BLS12-381 G1 MSM pairs/sec at
 2^20; Fr NTT 2^24 elems/sec (1/2/4/8 GPU)").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing more: it generates the inputs, warms
+up, times exactly --steps steps of the headline MSM, writes the last step's result if
+--dump-outputs is given, and prints the one JSON result line.  Every other line below (config5,
+NTT, config4, the host-buffer rates, the small sizes and the group FFT, the CPU baseline) runs
+only with --full, after the headline, and lands in the same result line.
 
 Workloads (synthetic, deterministic generator zk_gen.cpp: uniform Fr scalars in Montgomery
 form -- the Haskell `msm` path -- and an arithmetic progression of random order-r subgroup
@@ -25,7 +31,7 @@ points in affine Montgomery form; inputs resident in HBM when the timed region s
 Multi-GPU processes hold ONE HIP runtime (the library's, /opt/rocm) and never import torch: the
 rendezvous is a file (sharded.rendezvous_path), barrier / max-over-ranks / the exchange are the
 library's RCCL calls.  (--backend gloo: the torch.distributed CPU rehearsal used by the tests.)
-Rank 0 at N = 1 also reports the rate through the reference-named entry points with host
+With --full, rank 0 at N = 1 also reports the rate through the reference-named entry points with host
 buffers (what the Haskell binding pays: PCIe included) and the reference's own C
 (oracle/_ref, lib/cbits compiled in place) timed on host cores at the bench sizes.
 """
@@ -56,6 +62,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the secondary lines: config5, NTT, config4, the host-buffer "
+                         "(PCIe-inclusive) rates, the small MSM sizes, the group FFT and the CPU baseline "
+                         "(each can still be switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--curve", default="bls12_381", choices=["bls12_381", "bn128"])
     ap.add_argument("--log-n", type=int, default=20, help="log2 pairs PER GPU of the headline MSM")
     ap.add_argument("--window", type=int, default=0)
@@ -76,7 +88,10 @@ def parse():
     ap.add_argument("--backend", default="rccl", choices=["rccl", "gloo"],
                     help="exchange between ranks: rccl = the library's own RCCL communicator over xGMI; "
                          "gloo = torch.distributed on the CPU (rehearsals without GPUs)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def baseline():
@@ -231,6 +246,16 @@ def timed(dist, step, steps, warmup, sync, zk=None):
         out = step()
     sync()
     return dist.max(time.perf_counter() - t0) / steps, out
+
+
+def dump_outputs(path, aff):
+    """--dump-outputs: the array the caller of the timed step receives -- the affine sum (x, y) of
+    the last timed MSM, Montgomery form, as msm_affine.npy.  The u64 limbs are written as their
+    little-endian 32-bit halves in float64 (exact: every value is below 2^32), 2 * limbs numbers."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    words = np.ascontiguousarray(aff, dtype="<u8").view("<u4")
+    np.save(os.path.join(path, "msm_affine.npy"), words.astype(np.float64))
 
 
 def _free_port():
@@ -419,20 +444,23 @@ def main():
     result.update(msm_rooflines(curve, n_local, c, accum_s))
     d_s.free()
     d_p.free()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, aff)
 
-    if not args.no_config5 and curve == "bls12_381":
+    full = args.full  # the secondary lines: none of them feeds the headline figure
+    if full and not args.no_config5 and curve == "bls12_381":
         result["config5"] = bench_config5(zk, args, dist)
-    if not args.no_ntt:
+    if full and not args.no_ntt:
         result["ntt"] = bench_ntt(zk, args, dist)
-    if rank == 0 and world == 1 and curve == "bls12_381" and not args.no_config4:
+    if full and rank == 0 and world == 1 and curve == "bls12_381" and not args.no_config4:
         result["config4"] = bench_config4(zk)
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if full and rank == 0 and world == 1 and not args.no_e2e:
         result["end_to_end"] = end_to_end(zk, curve, scalars, points, ms_per_step, result.get("ntt"), args, aff)
-    if rank == 0 and world == 1 and not args.no_extras:
+    if full and rank == 0 and world == 1 and not args.no_extras:
         result["msm_sizes"] = bench_msm_sizes(zk)
         result["group_fft"] = bench_group_fft(zk)
         result["group_fft_kzg"] = bench_group_fft(zk, m=12, reps=5)  # KZG SRS size (examples/KZG.hs:55)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(zk, curve, seed, args.cpu_msm_log, args.cpu_ntt_log)
     if rank == 0:
         print(json.dumps(result), flush=True)

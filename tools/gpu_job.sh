@@ -7,7 +7,7 @@
 #   testsel   pytest -m gpu -k "$TESTSEL"         -> gpurun_out/TAG_testsel.log
 #   benchcomm bench.py --force-comm (the multi-GPU code path at world 1) -> gpurun_out/TAG_benchcomm.json
 #   smoke     __graft_entry__.smoke()             -> gpurun_out/TAG_smoke.log
-#   bench     python bench.py (defaults)          -> gpurun_out/TAG_bench.json
+#   bench     python bench.py --full (every line)  -> TAG_bench.json
 #   bench2    bench.py as 2 ranks on the one GPU (gloo exchange) -> gpurun_out/TAG_bench2.json
 #   bench2self  bench.py --gpus 2 started WITHOUT torchrun (bench.py's own launcher), gloo exchange
 #             -> gpurun_out/TAG_bench2self.json (must print n_gpus 2 and config5 parity true)
@@ -32,7 +32,7 @@ shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 O=gpurun_out/$TAG
-BENCH_SHORT="bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-config4 --no-config5 --ntt-steps 3 --no-extras"
+BENCH_SHORT="bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-config4 --no-config5 --ntt-steps 3 --no-extras"
 for step in "$@"; do
   echo "[$(date +%T)] step $step"
   case $step in
@@ -41,13 +41,13 @@ for step in "$@"; do
               --timeout-method thread > ${O}_testscomm.log 2>&1 ;;
     testsel) timeout -k 10 ${TESTS_TIMEOUT:-600} python -u -m pytest tests -x -v -m gpu -k "$TESTSEL" --timeout 120 \
               --timeout-method thread > ${O}_testsel.log 2>&1 ;;
-    benchcomm) timeout -k 10 300 python -u bench.py --force-comm --steps 10 --warmup 2 --no-e2e --no-cpu-baseline \
+    benchcomm) timeout -k 10 300 python -u bench.py --full --force-comm --steps 10 --warmup 2 --no-e2e --no-cpu-baseline \
               --no-config4 --ntt-steps 2 > ${O}_benchcomm.json 2> ${O}_benchcomm.err ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > ${O}_smoke.log 2>&1 ;;
-    bench) timeout -k 10 400 python -u bench.py > ${O}_bench.json 2> ${O}_bench.err ;;
+    bench) timeout -k 10 400 python -u bench.py --full > ${O}_bench.json 2> ${O}_bench.err ;;
     bench2) timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-              --master-port 29517 bench.py --gpus 2 --backend gloo --steps 3 --warmup 1 > ${O}_bench2.json 2> ${O}_bench2.err ;;
-    bench2self) timeout -k 10 600 python -u bench.py --gpus 2 --backend gloo --no-extras --no-e2e --no-cpu-baseline \
+              --master-port 29517 bench.py --full --gpus 2 --backend gloo --steps 3 --warmup 1 > ${O}_bench2.json 2> ${O}_bench2.err ;;
+    bench2self) timeout -k 10 600 python -u bench.py --full --gpus 2 --backend gloo --no-extras --no-e2e --no-cpu-baseline \
               --no-config4 --steps 5 --warmup 1 > ${O}_bench2self.json 2> ${O}_bench2self.err ;;
     bench2rccl) timeout -k 10 300 python -u bench.py --gpus 2 --no-extras --no-e2e --no-cpu-baseline --no-config4 \
               --no-config5 --no-ntt --steps 2 --warmup 1 > ${O}_bench2rccl.json 2> ${O}_bench2rccl.err
