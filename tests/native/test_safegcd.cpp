@@ -46,6 +46,18 @@ static void run(const char *name, const int64_t (&P)[L], uint64_t pinv, int n64,
   }
 }
 
+// Bernstein-Yang (safegcd, Theorem 11.2): ceil((49 d + 57) / 17) divsteps invert every input below a
+// d-bit modulus (d >= 46).  Each limb layout must run at least that many: batches x steps per batch.
+constexpr int divstep_bound(int d) { return (49 * d + 57 + 16) / 17; }
+#define CHECK_DIVSTEPS(FIELD, BITS)                                                                      \
+  static_assert(FIELD##_S62_BATCHES * 62 >= divstep_bound(BITS), #FIELD ": too few 62-step batches");   \
+  static_assert(FIELD##_S60_BATCHES * 60 >= divstep_bound(BITS), #FIELD ": too few 60-step batches")
+static_assert(divstep_bound(381) == 1102 && divstep_bound(255) == 739 && divstep_bound(254) == 736, "bound");
+CHECK_DIVSTEPS(ZK_BLS12_381_FP, 381);  // 60-step layout: 19 x 60 = 1140 >= 1102
+CHECK_DIVSTEPS(ZK_BLS12_381_FR, 255);  // 13 x 60 = 780 >= 739
+CHECK_DIVSTEPS(ZK_BN128_FP, 254);
+CHECK_DIVSTEPS(ZK_BN128_FR, 254);
+
 int main() {
   std::mt19937_64 rng(12345);
   {

@@ -169,6 +169,32 @@ def test_jac_fft_vs_reference(gpu, oracle, reference, curve, m):
         assert gpu.g1_fft_last_glv() == (1 if m > 0 else 0), (name, m)
 
 
+@pytest.mark.parametrize("curve", CURVES)
+def test_jac_fft_zero_one_zero_row_is_infinity(gpu, oracle, reference, curve):
+    """A Jacobian input row (0 : 1 : 0) -- what the reference's own normalize writes for infinity --
+    counts as the point at infinity here: any row with Z = 0 does (INTEGRATION.md:67-73).  This
+    deliberately differs from the reference's <C>_G1_jac_is_infinity (bls12_381_G1_jac.c:164-180,
+    bn128_G1_jac.c likewise), which also wants Y^2 = X^3 with X, Y non-zero, so that its add takes
+    (0 : 1 : 0) for a finite point and returns values that are no group sums.  The expected output is
+    therefore the reference's for the same input with that row written as its infinity (1 : 1 : 0)."""
+    m = 3
+    NP = gpu.NLIMBS_P[curve]
+    pts = jacobian(gpu, oracle, curve, 1 << m, 230 + m, n_inf=1)
+    one = gpu.batch_from_affine(curve, np.full((1, 2 * NP), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64), coords="jac")[0]
+    assert not one[2 * NP:].any() and np.array_equal(one[:NP], one[NP:2 * NP])  # (1 : 1 : 0), Montgomery
+    row = next(i for i in range(1 << m) if pts[i, 2 * NP:].any())  # a finite row
+    ours, theirs = pts.copy(), pts.copy()
+    ours[row] = 0
+    ours[row, NP:2 * NP] = one[:NP]  # (0 : 1 : 0)
+    theirs[row] = one
+    sg = gpu.get_fft_subgroup(curve, m)
+    for name, f in (("G1_jac_fft_forward", gpu.forward_fft), ("G1_jac_fft_inverse", gpu.inverse_fft)):
+        want = np.zeros_like(pts)
+        ref_call(reference, curve, name, m, sg.gen_array(), theirs, want)
+        assert np.array_equal(f(sg, ours, coords="jac"), want), name
+        assert gpu.g1_fft_last_glv() == 1, name
+
+
 @pytest.mark.parametrize("m", [1, 3, 6])
 def test_jac_fft_nonsubgroup_points_bls(gpu, oracle, reference, m):
     """Jacobian points outside the r-subgroup: the integer-scalar stages, the reference's exact schedule"""
