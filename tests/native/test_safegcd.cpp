@@ -1,17 +1,43 @@
 // Host check of zk_inv.hpp (the device inversion's code, compiled for the CPU): prints
 // "<field> <x> <x^-1>" lines in hex for tests/test_native.py to verify with Python big integers.
+// Lines "<field> <x>" (hex, below the modulus) on stdin are appended to the inputs of both limb
+// forms of that field: the edge values of tests/field_edges.py.
 #include <stdio.h>
 #include <stdint.h>
+#include <string.h>
+#include <map>
 #include <random>
+#include <string>
+#include <vector>
 #include "zk_inv.hpp"
 #include "zk_params.inc"
+
+struct Words { uint64_t w[6]; };
+static std::map<std::string, std::vector<Words>> extra;  // per field, from stdin
+
+static void read_extra() {
+  char name[64], hex[128];
+  while (scanf("%63s %127s", name, hex) == 2) {
+    Words v = {{0, 0, 0, 0, 0, 0}};
+    const int len = (int)strlen(hex);
+    for (int i = 0; i < len; i++) {  // hex digit i counts from the least significant end
+      const char ch = hex[len - 1 - i];
+      const uint64_t d = ch <= '9' ? ch - '0' : (ch | 32) - 'a' + 10;
+      if (i < 96) v.w[i / 16] |= d << (4 * (i % 16));
+    }
+    extra[name].push_back(v);
+  }
+}
 
 template <int L, int NB, int B = 62>
 static void run(const char *name, const int64_t (&P)[L], uint64_t pinv, int n64, const uint64_t *pw, int count,
                 std::mt19937_64 &rng) {
-  for (int k = 0; k < count; k++) {
+  const std::vector<Words> &ex = extra[name];
+  for (int k = 0; k < count + (int)ex.size(); k++) {
     uint64_t x[6] = {0, 0, 0, 0, 0, 0}, y[6];
-    if (k == 0) x[0] = 1;
+    if (k >= count) {
+      for (int i = 0; i < n64; i++) x[i] = ex[k - count].w[i];
+    } else if (k == 0) x[0] = 1;
     else if (k == 1) {  // p - 1
       for (int i = 0; i < n64; i++) x[i] = pw[i];
       x[0] -= 1;
@@ -59,6 +85,7 @@ CHECK_DIVSTEPS(ZK_BN128_FP, 254);
 CHECK_DIVSTEPS(ZK_BN128_FR, 254);
 
 int main() {
+  read_extra();
   std::mt19937_64 rng(12345);
   {
     static const int64_t P[] = ZK_BLS12_381_FP_S62_P;

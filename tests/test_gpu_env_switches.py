@@ -25,6 +25,7 @@ import sys
 import numpy as np
 import pytest
 
+import field_edges as fe
 import golden_io
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -471,6 +472,75 @@ def g2_msm(ctx, bt):
                                  pts=kp), w["proj"])
 
 
+# ---------------------------------------------------------------------------- edge values (tests/field_edges.py)
+def fr_edges(ctx, bt):
+    """the vectors of test_gpu_field_edges: every Fr op on the edge cross product E x E' with the
+    constants 0, R mod r, r - 1 and a random one, and inv / div over E \\ {0} with the zero rule;
+    expected values from the big-integer models"""
+    for curve in CURVES:
+        a, b, c, ks = fe.fr_cross(curve)
+        want = fe.fr_cross_expected(curve)
+        n = len(a)
+        K = {k: bt.put(f"fre_{curve}_{k}", fe.to_limbs(v, 4)) for k, v in (("a", a), ("b", b), ("c", c))}
+        kk = [bt.put(f"fre_{curve}_k{i}", fe.to_row(k, 4)) for i, k in enumerate(ks)]
+        for op in fe.UNARY + fe.BINARY + fe.TERNARY + ("dot",):
+            jid = bt.job(id=f"fre_{curve}_{op}", call="arr", curve=curve, op=op, n=n, **K)
+            bt.expect(jid, want[op][0] if op == "dot" else want[op])
+        for i in range(4):
+            for op in ("scale", "Ax_plus_y", "Ax_plus_By"):
+                jid = bt.job(id=f"fre_{curve}_{op}_{i}", call="arr", curve=curve, op=op, n=n, kA=kk[i],
+                             kB=kk[(i + 1) % 4], **K)
+                bt.expect(jid, want[f"{op}_{i}"])
+        M = fe.fr_model(curve)
+        for name, x, y in fe.inv_vectors(curve):
+            kx, ky = bt.put(f"fre_{curve}_{name}_x", fe.to_limbs(x, 4)), bt.put(f"fre_{curve}_{name}_y", fe.to_limbs(y, 4))
+            wi, wd = cached(("fre_inv", curve, name), lambda: (fe.to_limbs(M.inv(y), 4), fe.to_limbs(M.div(x, y), 4)))
+            bt.expect(bt.job(id=f"fre_{curve}_{name}_inv", call="arr", curve=curve, op="inv", a=ky), wi)
+            bt.expect(bt.job(id=f"fre_{curve}_{name}_div", call="arr", curve=curve, op="div", a=kx, b=ky), wd)
+
+
+def fp_edges(ctx, bt, chk=2):
+    """the off-curve Fp edge rows through batch_to_affine in both coordinate systems, and the
+    infinity layouts at n = 257 for lanes that own `chk` rows (2 by default; ZK_NORM_LANES=1 gives
+    chk = 32: whole 28- / 29-row lanes infinite, an infinity first and last in a lane); expected
+    values from the big-integer model"""
+    for curve in CURVES:
+        nl, M = ctx.gpu.NLIMBS_P[curve], fe.fp_model(curve)
+        for coords in ("proj", "jac"):
+            def edge_rows():
+                rows = fe.offcurve_rows(curve)
+                return fe.point_rows(rows, nl), fe.affine_rows(M, rows, coords)
+            pts, want = cached(("fpe", curve, coords), edge_rows)
+            tag = f"fpe_{curve}_{coords}"
+            bt.expect(bt.job(id=tag, call="to_affine", curve=curve, coords=coords, pts=bt.put(tag + "_in", pts)), want)
+
+            def layouts():
+                return [(name, p, fe.affine_rows(M, fe.point_ints(p, nl), coords))
+                        for name, p in fe.layout_rows(ctx.gpu, ctx.oracle, curve, coords, 257, chk, 957)]
+            for name, p, want in cached(("fpe_lay", curve, coords, chk), layouts):
+                tag = f"fpe_{curve}_{coords}_{chk}_{name}"
+                bt.expect(bt.job(id=tag, call="to_affine", curve=curve, coords=coords, pts=bt.put(tag + "_in", p)), want)
+
+
+def msm_digit_edges(ctx, bt):
+    """the 2^256 - 1 and alternating B / B + 1 digit patterns (256-bit std scalars, verbatim) at
+    c = 16 through the bucket pipeline, and as a default-window call (bit jobs; the bucket pipeline
+    under ZK_MSM_BITS_MAX=0), against the oracle"""
+    c, n = 16, 192
+    for curve in CURVES:
+        pts = cached(("dig_pts", curve), lambda: fe.digit_points(ctx.gpu.gen_points, curve, n))
+        kp = bt.put(f"dig_{curve}_pts", pts)
+        for name in ("all_ones", "alt_B_Bp1", "alt_Bp1_B", "rotated"):
+            sc = fe.digit_scalars(curve, c, name, n)
+            proj, aff = cached(("dig_want", curve, name), lambda: (
+                ctx.oracle.normalize(curve, ctx.oracle.msm(curve, sc, pts, mont=False, out="proj")),
+                ctx.oracle.msm(curve, sc, pts, mont=False)))
+            tag = f"dig_{curve}_{name}"
+            ks = bt.put(tag + "_sc", sc)
+            bt.expect(bt.job(id=tag + "_var", call="msm_variable", curve=curve, window=c, sc=ks, pts=kp), proj)
+            bt.expect(bt.job(id=tag + "_aff", call="msm_affine", curve=curve, std=True, sc=ks, pts=kp), aff)
+
+
 # ---------------------------------------------------------------------------- the table
 def _rows():
     rows = []
@@ -480,23 +550,23 @@ def _rows():
     # Fr element-wise ops: the four k_arr_op instantiations, each with its one-pass grid and with a
     # 3-workgroup grid (grid-stride loop, stage 4's software pipeline included); the round-5 kernel
     for stage in ("0", "1", "2", "4"):
-        add({"ZK_ARR_STAGE": stage}, fr_ops)
+        add({"ZK_ARR_STAGE": stage}, fr_ops, fr_edges)
         add({"ZK_ARR_STAGE": stage, "ZK_ARR_GRID": "3"}, fr_ops)
-    add({"ZK_ARR_MAP": "1"}, fr_ops)
+    add({"ZK_ARR_MAP": "1"}, fr_ops, fr_edges)
     # Fr batch inversion: the other three k_inv_chunks branches, CHK = clamp(n, 8, 128), and both.
     # ZK_INV_SG and ZK_INV_STRIDE are read by the batch affine conversion (and the FFT's closing
     # normalisation) as well.
-    add({"ZK_INV_SG": "0"}, fr_inv, to_affine, fft_norm)
-    add({"ZK_INV_STRIDE": "0"}, fr_inv, to_affine, fft_norm)
-    add({"ZK_INV_ILP": "0"}, fr_inv)
-    add({"ZK_INV_LANES": "1"}, fr_inv)
+    add({"ZK_INV_SG": "0"}, fr_inv, to_affine, fft_norm, fr_edges, fp_edges)
+    add({"ZK_INV_STRIDE": "0"}, fr_inv, to_affine, fft_norm, fp_edges)
+    add({"ZK_INV_ILP": "0"}, fr_inv, fr_edges)
+    add({"ZK_INV_LANES": "1"}, fr_inv, fr_edges)
     for flag in ("ZK_INV_SG", "ZK_INV_STRIDE", "ZK_INV_ILP"):
         add({flag: "0", "ZK_INV_LANES": "1"}, fr_inv)
     add({"ZK_VANISH_LEGACY": "1"}, vanish)
     add({"ZK_VANISH_STAGED": "1"}, vanish)
     # batch affine conversion: the other k_norm_chunks branches, chk = clamp(n, 2, 32), chk = 10
-    add({"ZK_NORM_BF": "0"}, to_affine, fft_norm)
-    add({"ZK_NORM_LANES": "1"}, to_affine, fft_norm)
+    add({"ZK_NORM_BF": "0"}, to_affine, fft_norm, fp_edges)
+    add({"ZK_NORM_LANES": "1"}, to_affine, fft_norm, lambda ctx, bt: fp_edges(ctx, bt, chk=32))
     add({"ZK_NORM_LANES": "100"}, to_affine, fft_norm)
     for flag in ("ZK_INV_SG", "ZK_INV_STRIDE", "ZK_NORM_BF"):
         add({flag: "0", "ZK_NORM_LANES": "1"}, to_affine, fft_norm)
@@ -512,15 +582,15 @@ def _rows():
     # =7: seven blocks.  ZK_MSM_BITS_MAX=0: the bucket pipeline at the default window for small n
     for g in ("1", "7"):
         add({"ZK_MSM_BITS_G": g}, lambda ctx, bt: msm_bits(ctx, bt, [256, 257, 511, 1000]))
-    add({"ZK_MSM_BITS_MAX": "0"}, lambda ctx, bt: msm_bits(ctx, bt, [1, 257, 4096]))
+    add({"ZK_MSM_BITS_MAX": "0"}, lambda ctx, bt: msm_bits(ctx, bt, [1, 257, 4096]), msm_digit_edges)
     # G1 MSM, bucket pipeline: the chunk rule's own lengths, both ends of the Y-sum bucket count,
     # both Y-sum kernels, the sort-ahead window groups
     for ch in ("4", "64", "128"):
-        add({"ZK_MSM_CH": ch}, msm_buckets)
+        add({"ZK_MSM_CH": ch}, msm_buckets, msm_digit_edges)
     for qy in ("1", "16"):  # 16 is also the value when the variable is unset: only 1 is a non-default path
         add({"ZK_YSUM_QY": qy}, msm_buckets)
     for mode in ("0", "1"):
-        add({"ZK_YSUM3": mode}, msm_buckets)
+        add({"ZK_YSUM3": mode}, msm_buckets, msm_digit_edges)
     add({"ZK_YSUM3_LANES": "1"}, msm_buckets)
     add({"ZK_MSM_AHEAD_MIN": "12"}, msm_buckets_device)
     # G1 MSM, host-buffer split pipeline

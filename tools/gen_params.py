@@ -116,6 +116,10 @@ def unsat_block(name, p):
     out.append(f"#define ZK_{P}_S60_L {L60}")
     out.append(f"#define ZK_{P}_S60_P {{ {vals} }}")
     out.append(f"#define ZK_{P}_S60_BATCHES {-(-steps // 60)}")
+    # both layouts run at least the Bernstein-Yang bound ceil((49 d + 57) / 17) of divsteps:
+    # 381 bits: 18 x 62 = 1116, 19 x 60 = 1140 >= 1102; 255 bits: 12 x 62 = 744, 13 x 60 = 780 >= 739
+    bound = -(-(49 * nbits + 57) // 17)
+    assert -(-steps // 62) * 62 >= bound and -(-steps // 60) * 60 >= bound, name
     return out
 
 

@@ -682,9 +682,12 @@ __device__ __forceinline__ void fe_store_ref(uint64_t *__restrict__ p, const Fe<
 
 // Inverse in internal form by safegcd (zk_inv.hpp): a = x R' (any value < 2p, normalised limbs) ->
 // x^-1 R' (< 2p).  canon(a) = x R' mod p as an integer; b = (x R')^-1 mod p by divsteps; one product
-// by R'^3 gives x^-1 R'.  a = 0 gives 0.  19 / 13 batches of 2 x 30 divsteps on 60-bit limbs (381- /
-// 255-bit fields; ZK_INV_DS30, the default) or 18 / 12 batches of 62 (ZK_INV_DS30=0), instead of a
-// 489 / 323-product Fermat chain (round 6).
+// by R'^3 gives x^-1 R'.  a = 0 gives 0.  The default (ZK_INV_DS30 = 1) runs batches of 2 x 30
+// divsteps on 60-bit limbs: 19 batches for the 381-bit field and 13 for the 254- / 255-bit fields,
+// i.e. 1140 >= 1102 and 780 >= 739 (>= 736) steps, where ceil((49 d + 57) / 17) is the Bernstein-Yang
+// bound for a d-bit modulus.  ZK_INV_DS30 = 0 runs 18 / 12 batches of 62 (1116 / 744 steps).  Both
+// counts are asserted where they are emitted (tools/gen_params.py) and in
+// tests/test_field_edges_cpu.py.  Either replaces a 489 / 323-product Fermat chain (round 6).
 #ifndef ZK_INV_DS30
 #define ZK_INV_DS30 1  // 60-bit limbs, batches of 2 x 30 divsteps in 32-bit arithmetic; 0: 62 in 64-bit
 #endif
