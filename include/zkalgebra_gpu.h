@@ -93,6 +93,18 @@ ZKG_API void bls12_381_G2_proj_MSM_std_coeff_proj_out(int npoints, const uint64_
 ZKG_API void bls12_381_G2_proj_MSM_mont_coeff_proj_out(int npoints, const uint64_t *expos, const uint64_t *grps, uint64_t *tgt, int expo_nlimbs);
 ZKG_API void bls12_381_G2_proj_MSM_std_coeff_affine_out (int npoints, const uint64_t *expos, const uint64_t *grps, uint64_t *tgt, int expo_nlimbs);
 ZKG_API void bls12_381_G2_proj_MSM_mont_coeff_affine_out(int npoints, const uint64_t *expos, const uint64_t *grps, uint64_t *tgt, int expo_nlimbs);
+/* explicit window (bls12_381_G2_proj.c:498): clamped to 4..24 like the G1 twin; the result does not depend on it */
+ZKG_API void bn128_G2_proj_MSM_std_coeff_proj_out_variable(int npoints, const uint64_t *expos, const uint64_t *grps, uint64_t *tgt, int expo_nlimbs, int window_size);
+ZKG_API void bls12_381_G2_proj_MSM_std_coeff_proj_out_variable(int npoints, const uint64_t *expos, const uint64_t *grps, uint64_t *tgt, int expo_nlimbs, int window_size);
+
+/* G2 batch conversions (bls12_381_G2_proj.h:9-10; Haskell batchFromAffine / batchToAffine,
+ * G2/Proj.hs:386-405, and msmProj = msm . batchToAffine, :223-224).  Host buffers; rows are
+ * 4 NP (affine) and 6 NP (projective) words.  Affine infinity (all-0xFF) <-> (0 : 1 : 0); every
+ * row with Z = 0 converts to all-0xFF.  One Fp inversion is shared by many points. */
+ZKG_API void bn128_G2_proj_batch_from_affine( int N, const uint64_t *src , uint64_t *tgt );
+ZKG_API void bn128_G2_proj_batch_to_affine  ( int N, const uint64_t *src , uint64_t *tgt );
+ZKG_API void bls12_381_G2_proj_batch_from_affine( int N, const uint64_t *src , uint64_t *tgt );
+ZKG_API void bls12_381_G2_proj_batch_to_affine  ( int N, const uint64_t *src , uint64_t *tgt );
 
 /* G1 batch conversions and the group (curve) FFT.
  *   bls12_381_G1_proj.h:9-10, 48-49 (bn128_G1_proj.h same lines); Haskell batchFromAffine /
@@ -308,6 +320,8 @@ ZKG_API void zkg_g1_batch_to_affine_device(int curve, int n, const uint64_t *d_s
 ZKG_API void zkg_g1_jac_fft_device(int curve, int inverse, int m, const uint64_t *gen, const uint64_t *d_src,
                                    uint64_t *d_tgt);
 ZKG_API void zkg_g1_jac_batch_to_affine_device(int curve, int n, const uint64_t *d_src, uint64_t *d_tgt);
+/* device-resident G2 batch_to_affine: n projective rows (6 NP words) -> n affine rows (4 NP words) */
+ZKG_API void zkg_g2_batch_to_affine_device(int curve, int n, const uint64_t *d_src, uint64_t *d_tgt);
 
 /* host helpers on G1 (projective, reference Montgomery form) */
 ZKG_API void zkg_g1_proj_add(int curve, const uint64_t *a, const uint64_t *b, uint64_t *out);

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Measurement of the SURVEY.md 8f rows (GPU box): Fr vector ops, division by a
-vanishing polynomial, G1 batch_to_affine, G1 group FFT, G2 MSM.
+vanishing polynomial, G1 batch_to_affine, G1 group FFT, G2 MSM, G2 batch_to_affine and msmProj
+on projective G2 rows (--g2ext-only: these last lines alone).
 
 Every GPU figure is device-resident (inputs already in HBM, hipDeviceSynchronize around
 the timed loop); HBM rooflines use ALGORITHMIC bytes (operands read once + result written
@@ -63,15 +64,57 @@ def hbm(bytes_, sec):
     return {"bound": "hbm", "achieved": gbs, "peak": HBM, "unit": "GB/s", "frac": gbs / HBM}
 
 
+def g2ext(ref, quick):
+    """G2 batch_to_affine (device-resident) and msmProj on projective G2 rows (host arrays in, point
+    out), both curves; distinct rows P0 + i H from the reference's own arithmetic, Z non-trivial"""
+    from test_gpu_g2ext import progression
+    lib = zk.load()
+    res = {}
+    n = 1 << (16 if quick else 20)
+    for curve in ("bls12_381", "bn128"):
+        cid, NP = zk.CURVE_ID[curve], zk.NLIMBS_P[curve]
+        t0 = time.perf_counter()
+        proj = progression(ref.lib, curve, n)
+        gen_s = time.perf_counter() - t0
+        sc = zk.gen_fr(curve, 9, n)
+        dpj, daf, dsc = zk.DeviceBuffer(proj), zk.DeviceBuffer.empty(n * 4 * NP * 8), zk.DeviceBuffer(sc)
+        sec = timeit(lambda: lib.zkg_g2_batch_to_affine_device(cid, n, dpj.ptr, daf.ptr), 5)
+        row = {"n": n, "ms": sec * 1e3, "points_per_s": n / sec, "roofline": hbm(18 * NP * 8 * n, sec),
+               "roofline_note": "bytes the two kernels move, in Fp elements per point: the chain reads Z twice "
+                                "(4) and writes its scratch twice and reads it once (3); the apply kernel reads "
+                                "the row (6) and the scratch (1) and writes the affine row (4)",
+               "note": f"{n} distinct reference-generated projective rows (generated in {gen_s:.0f} s on the host)"}
+        out_pt = np.zeros(6 * NP, np.uint64)
+        sec = timeit(lambda: lib.zkg_g2_msm_device(cid, n, dsc.ptr, 4, 1, daf.ptr, out_pt.ctypes.data_as(zk.U64P), 0), 3)
+        row["g2_msm_device_ms"] = sec * 1e3
+        for d in (dpj, daf, dsc):
+            d.free()
+        sec = timeit(lambda: zk.g2_msm_proj(curve, sc, proj), 3)
+        row["g2_msm_proj_end_to_end_ms"] = sec * 1e3
+        s = 1 << 12
+        w = np.zeros((s, 4 * NP), np.uint64)
+        t = cpu_time(lambda: ref.arr(curve, "G2_proj_batch_to_affine", s, proj[:s], w))
+        row["cpu_reference"] = {"points_per_s": s / t, "cores": 1, "sample": "first 2^12 rows",
+                                "seconds_for_n": n / (s / t)}
+        res[curve] = row
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--g2ext-only", action="store_true", help="only the G2 batch conversion / msmProj lines")
     args = ap.parse_args()
     zk.require_gpu()
     ref = Reference() if Reference.available() else None
     out = {"curve": CURVE, "data": "synthetic (zk_gen.cpp generator; G2 points from the reference's generator)"}
     lib = zk.load()
     P = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    if args.g2ext_only:
+        if not ref:
+            sys.exit("the G2 lines need the reference build (oracle/_ref) for their inputs")
+        print(json.dumps({"g2_batch_to_affine": g2ext(ref, args.quick)}), flush=True)
+        return
 
     # ---------------------------------------------------------------- Fr vector ops, 2^24
     m = 22 if args.quick else 24
@@ -218,6 +261,8 @@ def main():
             out["g2_msm"][f"{curve}_2^{gm}"] = g2
             dsc.free()
             dpt.free()
+    if ref:
+        out["g2_batch_to_affine"] = g2ext(ref, args.quick)
     print(json.dumps(out), flush=True)
 
 

@@ -4,6 +4,8 @@
 //   <C>_G1_proj_MSM_{mont,std}_coeff_{proj,affine}_out  bls12_381_G1_proj.c:597-670
 //   <C>_G1_proj_MSM_std_coeff_proj_out_variable          bls12_381_G1_proj.c:507
 //   <C>_G1_jac_MSM_{mont,std}_coeff_{jac,affine}_out    bls12_381_G1_jac.c:555-718
+//   <C>_G2_proj_MSM_{mont,std}_coeff_{proj,affine}_out  bls12_381_G2_proj.c:588-660
+//   <C>_G2_proj_MSM_std_coeff_proj_out_variable          bls12_381_G2_proj.c:498
 //   <C>_poly_mont_ntt_{forward,inverse}                  bls12_381_poly_mont.c:457,516
 // Every one of them runs on the GPU; there is no CPU fallback path.
 #include <hip/hip_runtime.h>
@@ -118,6 +120,12 @@ ZKG_MSM_ENTRIES(bls12_381, BLS381)
   ZKG_API void PFX##_G2_proj_MSM_std_coeff_affine_out(int n, const uint64_t *e, const uint64_t *g, uint64_t *t,  \
                                                       int nl) {                                                 \
     msm_entry<CURVE>(n, e, g, t, nl, false, 0, AFFINE);                                                        \
+  }                                                                                                             \
+  /* bls12_381_G2_proj.c:498; the window is clamped as for G1, the result does not depend on it */             \
+  ZKG_API void PFX##_G2_proj_MSM_std_coeff_proj_out_variable(int n, const uint64_t *e, const uint64_t *g,       \
+                                                             uint64_t *t, int nl, int window) {                 \
+    int c = window < 4 ? 4 : (window > 24 ? 24 : window);                                                       \
+    msm_entry<CURVE>(n, e, g, t, nl, false, c, PROJ);                                                          \
   }
 
 ZKG_G2_MSM_ENTRIES(bn128, BN254_G2)

@@ -200,3 +200,26 @@ ZKG_API void zkg_g1_jac_batch_to_affine_device(int curve, int n, const uint64_t 
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------- G2 batch conversions
+// <C>_G2_proj_batch_from_affine / _batch_to_affine (bls12_381_G2_proj.c:139-158; G2/Proj.hs:386-405)
+#include "zk_g2ext.hpp"
+
+extern "C" {
+
+#define ZKG_G2EXT_ENTRIES(PFX, CID)                                                            \
+  ZKG_API void PFX##_G2_proj_batch_from_affine(int N, const uint64_t *src, uint64_t *tgt) {    \
+    guard([&] { zk::g2_batch_from_affine(CID, N, src, tgt, true); });                          \
+  }                                                                                            \
+  ZKG_API void PFX##_G2_proj_batch_to_affine(int N, const uint64_t *src, uint64_t *tgt) {      \
+    guard([&] { zk::g2_batch_to_affine(CID, N, src, tgt, true); });                            \
+  }
+
+ZKG_G2EXT_ENTRIES(bn128, ZKG_BN128)
+ZKG_G2EXT_ENTRIES(bls12_381, ZKG_BLS12_381)
+
+ZKG_API void zkg_g2_batch_to_affine_device(int curve, int n, const uint64_t *d_src, uint64_t *d_tgt) {
+  guard([&] { zk::g2_batch_to_affine(curve, n, d_src, d_tgt, false); });
+}
+
+}  // extern "C"

@@ -40,16 +40,13 @@
 #include <cstring>
 #include <vector>
 #include "zk_curve.hpp"
+#include "zk_extdev.hpp"
 #include "zk_host.hpp"
 #include "zk_msm.hpp"
 #include "zk_runtime.hpp"
 #include "zk_g1ext.hpp"
 
 namespace zk {
-
-struct W6 {
-  uint64_t w[6];
-};
 
 template <class F>
 constexpr int xw() { return xyzz_words<F>(); }  // u32 words per stored XYZZ point
@@ -58,25 +55,6 @@ constexpr int xw() { return xyzz_words<F>(); }  // u32 words per stored XYZZ poi
 template <class F, int NW>
 __device__ __forceinline__ void fe_pow_words(Fe<F> &r, const Fe<F> &x, const W6 &e) {
   fe_pow_sw(r, x, e.w, NW);
-}
-
-template <class F>
-__device__ __forceinline__ void ld_int(Fe<F> &r, const uint64_t *p) {  // reference form -> internal
-  Fe<F> t;
-  fe_load_ref(t, p);
-  fe_to_int(r, t);
-}
-template <class F>
-__device__ __forceinline__ void st_ref(uint64_t *p, const Fe<F> &a) {  // internal -> canonical reference form
-  Fe<F> t;
-  fe_to_ref(t, a);
-  fe_store_ref(p, t);
-}
-template <class F>
-__device__ __forceinline__ bool ref_all_ones(const uint64_t *p, int words) {
-  uint64_t a = ~0ull;
-  for (int i = 0; i < words; i++) a &= p[i];
-  return a == ~0ull;
 }
 
 // ---------------------------------------------------------------------------- batch_from_affine
@@ -107,20 +85,7 @@ enum { MODE_PROJ_TO_AFF = 0, MODE_XYZZ_TO_PROJ = 1, MODE_JAC_TO_AFF = 2 };
 
 // Round 6: the chunk of lane t is the strided set {t, t + T, ...} (T = lanes, as k_inv_chunks):
 // neighbouring lanes touch neighbouring point rows.  STRIDED = false: CHK consecutive points.
-// canonical reference-form words of a (internal form), or `alt` where !keep, stored as 16-B runs
-template <class F>
-__device__ __forceinline__ void st_ref_or(uint64_t *p, const Fe<F> &a, bool keep, const uint32_t (&alt)[F::NW]) {
-  Fe<F> t;
-  fe_to_ref(t, a);
-  fe_canon(t);
-  uint32_t w[F::NW];
-  fe_pack(w, t);
-#pragma unroll
-  for (int i = 0; i < F::NW; i++) w[i] = keep ? w[i] : alt[i];
-  uint4 *q = reinterpret_cast<uint4 *>(p);
-#pragma unroll
-  for (int i = 0; i < F::NW / 4; i++) q[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
-}
+// (st_ref_or, zk_extdev.hpp: a row's canonical words, or the infinity pattern, stored as 16-B runs)
 // BF (round 6, default; ZK_NORM_BF=0 restores the branches): every step branch-free -- the points at
 // infinity take the factor 1 and have their output rows selected word by word, and every load and
 // store is unconditional, so no path merge inside the loop makes the compiler wait for all
@@ -1371,7 +1336,7 @@ static void launch_norm(hipStream_t st, int n, int chk, const void *src, uint64_
                        pm2, bitrev_m, (int)lanes);
   ZK_CHECK(hipGetLastError());
 }
-static int norm_chk(size_t N) {
+int norm_chk(size_t N) {
   static const size_t target = [] {
     const char *e = getenv("ZK_NORM_LANES");
     const long v = e ? atol(e) : 0;

@@ -1,9 +1,14 @@
 // zk_g1ext.hpp -- C++ interface of the G1 batch conversions and the group FFT (zk_g1ext.hip)
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <atomic>
 
 namespace zk {
+
+// points per shared inversion of an N-row batch conversion (N / ZK_NORM_LANES within [2, 32]);
+// the G2 conversion (zk_g2ext.hip) sizes its chunks with it as well
+int norm_chk(size_t N);
 
 // affine (x || y, all-0xFF = infinity) -> projective (x : y : 1), infinity -> (0 : 1 : 0);
 // jac: Jacobian (x : y : 1), infinity -> (1 : 1 : 0)

@@ -51,7 +51,9 @@ REFERENCE_SYMBOLS += [f"{c}_arr_mont_{o}" for c in CURVES for o in ARR_OPS] + [
     f"{c}_poly_mont_{k}_by_vanishing" for c in CURVES for k in ("div", "quot")] + [
     f"{c}_G1_{co}_{f}" for c in CURVES for co in ("proj", "jac")
     for f in ("batch_from_affine", "batch_to_affine", "fft_forward", "fft_inverse")] + [
-    f"{c}_G2_proj_MSM_{k}_coeff_{o}_out" for c in CURVES for k in ("mont", "std") for o in ("proj", "affine")]
+    f"{c}_G2_proj_MSM_{k}_coeff_{o}_out" for c in CURVES for k in ("mont", "std") for o in ("proj", "affine")] + [
+    f"{c}_G2_proj_{f}" for c in CURVES
+    for f in ("batch_from_affine", "batch_to_affine", "MSM_std_coeff_proj_out_variable")]
 EXTENSION_SYMBOLS = [
     "zkg_version", "zkg_device_count", "zkg_set_device", "zkg_device_malloc", "zkg_device_free",
     "zkg_memcpy_htod", "zkg_memcpy_dtoh", "zkg_device_synchronize", "zkg_g1_msm_device", "zkg_ntt_device",
@@ -64,7 +66,7 @@ EXTENSION_SYMBOLS = [
     "zkg_arena_set_limit", "zkg_msm_last_groups", "zkg_g1_fft_last_glv", "zkg_g1_fft_plan", "zkg_g1_fft_radix_products", "zkg_msm_workspace_bytes", "zkg_set_devices", "zkg_get_devices",
     "zkg_release", "zkg_comm_unique_id", "zkg_comm_init", "zkg_comm_destroy", "zkg_comm_rank", "zkg_comm_world",
     "zkg_comm_allgather", "zkg_comm_barrier", "zkg_comm_max_f64", "zkg_g1_comm_sum_partials",
-    "zkg_g1_msm_device_sharded", "zkg_set_error_mode", "zkg_last_error",
+    "zkg_g1_msm_device_sharded", "zkg_set_error_mode", "zkg_last_error", "zkg_g2_batch_to_affine_device",
 ]
 
 _lib = None
@@ -87,6 +89,8 @@ def load():
                                           ctypes.c_void_p, U64P, ctypes.c_int]
         lib.zkg_ntt_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, U64P, ctypes.c_void_p,
                                        ctypes.c_void_p]
+        lib.zkg_g2_msm_device.argtypes = lib.zkg_g1_msm_device.argtypes
+        lib.zkg_g2_batch_to_affine_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         lib.zkg_gen_fr.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, U64P]
         lib.zkg_gen_g1_points.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, U64P]
         lib.zkg_timer_read.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
@@ -246,6 +250,80 @@ def g2_msm(curve, coeffs, points, std=False, affine=False):
     out = np.zeros((4 if affine else 6) * NLIMBS_P[curve], dtype=np.uint64)
     name = f"{curve}_G2_proj_MSM_{'std' if std else 'mont'}_coeff_{'affine' if affine else 'proj'}_out"
     getattr(load(), name)(coeffs.shape[0], _p(coeffs), _p(points), _p(out), coeffs.shape[1])
+    return out
+
+
+def g2_msm_variable(curve, coeffs, points, window_size):
+    """<C>_G2_proj_MSM_std_coeff_proj_out_variable (bls12_381_G2_proj.c:498; exported, unbound by Haskell)."""
+    if coeffs.ndim != 2 or points.ndim != 2 or coeffs.shape[0] != points.shape[0]:
+        raise ValueError("msm: incompatible array dimensions")
+    if points.shape[1] != 4 * NLIMBS_P[curve]:
+        raise ValueError("msm: G2 points must be affine (x, y) over Fp2 in Montgomery form")
+    require_gpu()
+    out = np.zeros(6 * NLIMBS_P[curve], dtype=np.uint64)
+    getattr(load(), f"{curve}_G2_proj_MSM_std_coeff_proj_out_variable")(
+        coeffs.shape[0], _p(coeffs), _p(points), _p(out), coeffs.shape[1], int(window_size))
+    return out
+
+
+def _g2_rows(name, a, words):
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if a.ndim != 2 or a.shape[1] != words:
+        raise ValueError(f"{name}: G2 rows must have {words} limbs")
+    return a
+
+
+def g2_batch_from_affine(curve, aff):
+    """G2 Proj.batchFromAffine (G2/Proj.hs:386-394): infinity (all-0xFF) -> (0 : 1 : 0)"""
+    aff = _g2_rows("batchFromAffine", aff, 4 * NLIMBS_P[curve])
+    require_gpu()
+    out = np.zeros((aff.shape[0], 6 * NLIMBS_P[curve]), dtype=np.uint64)
+    getattr(load(), f"{curve}_G2_proj_batch_from_affine")(aff.shape[0], _p(aff), _p(out))
+    return out
+
+
+def g2_batch_to_affine(curve, proj):
+    """G2 Proj.batchToAffine (G2/Proj.hs:396-405): Z = 0 -> all-0xFF"""
+    proj = _g2_rows("batchToAffine", proj, 6 * NLIMBS_P[curve])
+    require_gpu()
+    out = np.zeros((proj.shape[0], 4 * NLIMBS_P[curve]), dtype=np.uint64)
+    getattr(load(), f"{curve}_G2_proj_batch_to_affine")(proj.shape[0], _p(proj), _p(out))
+    return out
+
+
+def g2_msm_proj(curve, coeffs, proj_points, std=False, affine=False):
+    """G2 Proj.msmProj cs gs = msm cs (batchToAffine gs) (G2/Proj.hs:223-224).  The projective rows
+    are uploaded once, converted on the device (zkg_g2_batch_to_affine_device) and fed to the
+    device-resident MSM, so the affine array never crosses the host link."""
+    if coeffs.ndim != 2 or proj_points.ndim != 2 or coeffs.shape[0] != proj_points.shape[0]:
+        raise ValueError("msm: incompatible array dimensions")
+    if proj_points.shape[1] != 6 * NLIMBS_P[curve]:
+        raise ValueError("msm: G2 points must be projective (X, Y, Z) over Fp2 in Montgomery form")
+    if coeffs.shape[1] < 1:
+        raise ValueError("msm: coefficients need at least one limb")
+    require_gpu()
+    lib, cid, NP = load(), CURVE_ID[curve], NLIMBS_P[curve]
+    n = coeffs.shape[0]
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
+    proj_points = np.ascontiguousarray(proj_points, dtype=np.uint64)
+    res = np.zeros(6 * NP, dtype=np.uint64)
+    bufs = []
+    try:
+        bufs.append(DeviceBuffer(coeffs))
+        bufs.append(DeviceBuffer(proj_points))
+        bufs.append(DeviceBuffer.empty(n * 4 * NP * 8))
+        d_sc, d_proj, d_aff = bufs
+        lib.zkg_g2_batch_to_affine_device(cid, n, d_proj.ptr, d_aff.ptr)
+        lib.zkg_g2_msm_device(cid, n, d_sc.ptr, coeffs.shape[1], 0 if std else 1, d_aff.ptr, _p(res), 0)
+    finally:
+        for b in bufs:
+            b.free()
+    if not affine:
+        return res  # normalised by zkg_g2_msm_device
+    # (x : y : 1) or (0 : 1 : 0) -> affine, as the host-side conversion of the G2 entry points
+    out = np.full(4 * NP, np.uint64(0xFFFFFFFFFFFFFFFF), dtype=np.uint64)
+    if res[4 * NP:].any():
+        out[:] = res[:4 * NP]
     return out
 
 
