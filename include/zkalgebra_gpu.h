@@ -222,6 +222,37 @@ ZKG_API void bls12_381_arr_mont_Ax_plus_By_inplace ( int n, const uint64_t *coef
 ZKG_API void bls12_381_poly_mont_div_by_vanishing ( int n1, const uint64_t *src1, int expo_n, const uint64_t *eta, int nquot, uint64_t *quot, int nrem, uint64_t *rem );
 ZKG_API uint8_t bls12_381_poly_mont_quot_by_vanishing( int n1, const uint64_t *src1, int expo_n, const uint64_t *eta, int nquot, uint64_t *quot );
 
+
+/* Polynomial layer over Fr (lib/cbits/curves/poly/mont/bls12_381_poly_mont.c:26-243, bn128 same
+ * lines; Poly.hs:199-209).  Parameter types are those of the DEFINITIONS in the .c file and of
+ * the Haskell foreign imports: the reference header declares degree(const uint64_t*) without the
+ * length, the .c file and Poly.hs:199 have (int, const uint64_t*), which is what is exported here.
+ * mul_naive is what Haskell's (*) and sqr on Poly call (Poly.hs:133); it computes the same
+ * coefficients by a direct kernel (short factor) or by NTTs, so n1 + n2 - 1 is limited to 2^28
+ * (bn128) / 2^30 (bls12_381): beyond it the call fails through the error channel.  src1 == src2
+ * is allowed; tgt aliases no input of mul_naive, lincomb and eval_at.  get_coeff, is_constant,
+ * long_div, quot and rem are NOT provided. */
+ZKG_API int     bn128_poly_mont_degree   ( int n1, const uint64_t *src1 );
+ZKG_API uint8_t bn128_poly_mont_is_zero  ( int n1, const uint64_t *src1 );
+ZKG_API uint8_t bn128_poly_mont_is_equal ( int n1, const uint64_t *src1, int n2, const uint64_t *src2 );
+ZKG_API void    bn128_poly_mont_neg      ( int n1, const uint64_t *src1, uint64_t *tgt );
+ZKG_API void    bn128_poly_mont_add      ( int n1, const uint64_t *src1, int n2, const uint64_t *src2, uint64_t *tgt );
+ZKG_API void    bn128_poly_mont_sub      ( int n1, const uint64_t *src1, int n2, const uint64_t *src2, uint64_t *tgt );
+ZKG_API void    bn128_poly_mont_scale    ( const uint64_t *kst1, int n2, const uint64_t *src2, uint64_t *tgt );
+ZKG_API void    bn128_poly_mont_lincomb  ( int K, const int *ns, const uint64_t **coeffs, const uint64_t **polys, uint64_t *tgt );
+ZKG_API void    bn128_poly_mont_mul_naive( int n1, const uint64_t *src1, int n2, const uint64_t *src2, uint64_t *tgt );
+ZKG_API void    bn128_poly_mont_eval_at  ( int n1, const uint64_t *src1, const uint64_t *loc, uint64_t *tgt );
+ZKG_API int     bls12_381_poly_mont_degree   ( int n1, const uint64_t *src1 );
+ZKG_API uint8_t bls12_381_poly_mont_is_zero  ( int n1, const uint64_t *src1 );
+ZKG_API uint8_t bls12_381_poly_mont_is_equal ( int n1, const uint64_t *src1, int n2, const uint64_t *src2 );
+ZKG_API void    bls12_381_poly_mont_neg      ( int n1, const uint64_t *src1, uint64_t *tgt );
+ZKG_API void    bls12_381_poly_mont_add      ( int n1, const uint64_t *src1, int n2, const uint64_t *src2, uint64_t *tgt );
+ZKG_API void    bls12_381_poly_mont_sub      ( int n1, const uint64_t *src1, int n2, const uint64_t *src2, uint64_t *tgt );
+ZKG_API void    bls12_381_poly_mont_scale    ( const uint64_t *kst1, int n2, const uint64_t *src2, uint64_t *tgt );
+ZKG_API void    bls12_381_poly_mont_lincomb  ( int K, const int *ns, const uint64_t **coeffs, const uint64_t **polys, uint64_t *tgt );
+ZKG_API void    bls12_381_poly_mont_mul_naive( int n1, const uint64_t *src1, int n2, const uint64_t *src2, uint64_t *tgt );
+ZKG_API void    bls12_381_poly_mont_eval_at  ( int n1, const uint64_t *src1, const uint64_t *loc, uint64_t *tgt );
+
 /* ------------------------------------------------------------------------------
  * Part 2: extensions (not in the reference).  curve: 0 = bn128, 1 = bls12_381.
  * ---------------------------------------------------------------------------- */
@@ -311,6 +342,20 @@ ZKG_API void zkg_arr_powers_device(int curve, int n, const uint64_t *kA, const u
 ZKG_API int zkg_poly_div_by_vanishing_device(int curve, int n1, const uint64_t *d_src, int expo_n,
                                              const uint64_t *eta, int nquot, uint64_t *d_quot, int nrem,
                                              uint64_t *d_rem);
+
+/* polynomial layer on device-resident operands (zk_poly.hip).  zkg_poly_mul_device returns 0, or
+ * -1 (nothing done) when n1 + n2 - 1 exceeds 2^28 (bn128) / 2^30 (bls12_381); d_a == d_b squares;
+ * d_tgt (n1 + n2 - 1 rows) aliases neither.  x, tgt of eval and coeffs (K x 4 words), ns and the
+ * array d_polys of K device pointers of lincomb are HOST memory. */
+ZKG_API int zkg_poly_mul_device(int curve, int n1, const uint64_t *d_a, int n2, const uint64_t *d_b, uint64_t *d_tgt);
+ZKG_API void zkg_poly_eval_device(int curve, int n, const uint64_t *d_poly, const uint64_t *x, uint64_t *tgt);
+ZKG_API void zkg_poly_lincomb_device(int curve, int K, const int *ns, const uint64_t *coeffs, const uint64_t *const *d_polys, uint64_t *d_tgt);
+/* test hooks: a product whose shorter factor has <= len coefficients takes the direct kernel
+ * (0: always the transform, < 0: the default); the path of the most recent product (0: direct,
+ * else log2 of the transform size) */
+ZKG_API void zkg_poly_set_mul_direct_max(int len);
+ZKG_API int zkg_poly_last_mul_path(void);
+
 
 /* device-resident G1 group FFT / batch_to_affine (d_* DEVICE pointers, gen on the host) */
 ZKG_API void zkg_g1_fft_device(int curve, int inverse, int m, const uint64_t *gen, const uint64_t *d_src,

@@ -100,8 +100,93 @@ def g2ext(ref, quick):
     return res
 
 
+def poly_rows(ref, quick):
+    """polynomial layer (zk_poly.hip), device-resident: the product against the same product composed
+    from the public device calls (zero-padded copies, zkg_ntt_device x 2, zkg_arr_op_device mul,
+    zkg_ntt_device inverse), eval_at against zkg_arr_powers_device + zkg_arr_dot_device, lincomb with
+    K = 8; the composition is timed `rounds` times and its spread recorded as the margin"""
+    lib = zk.load()
+    cid = zk.CURVE_ID[CURVE]
+    P = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    res = {"product": {}, "eval_at": {}}
+    one = np.zeros(4, np.uint64)
+    lib.zkg_gen_fr(cid, 1, 0, 1, P(one))
+    rounds, reps = 5, 5 if quick else 20
+    for lg in (12, 16) if quick else (12, 16, 20):
+        n = 1 << lg
+        a, b = zk.gen_fr(CURVE, 3, n), zk.gen_fr(CURVE, 4, n)
+        da, db, dt = zk.DeviceBuffer(a), zk.DeviceBuffer(b), zk.DeviceBuffer.empty(2 * n * 32)
+        zero = np.zeros((2 * n, 4), np.uint64)
+        pa, pb, pc = zk.DeviceBuffer(zero), zk.DeviceBuffer(zero), zk.DeviceBuffer(zero)
+        gen = zk.get_fft_subgroup(CURVE, lg + 1).gen_array()
+
+        def composed():
+            lib.zkg_arr_op_device(cid, zk.ARR_OP_CODE["copy"], n, da.ptr, None, None, P(one), P(one), pa.ptr)
+            lib.zkg_arr_op_device(cid, zk.ARR_OP_CODE["copy"], n, db.ptr, None, None, P(one), P(one), pb.ptr)
+            lib.zkg_ntt_device(cid, 0, lg + 1, P(gen), pa.ptr, pc.ptr)
+            lib.zkg_ntt_device(cid, 0, lg + 1, P(gen), pb.ptr, pa.ptr)
+            lib.zkg_arr_op_device(cid, zk.ARR_OP_CODE["mul"], 2 * n, pc.ptr, pa.ptr, None, P(one), P(one), pb.ptr)
+            lib.zkg_ntt_device(cid, 1, lg + 1, P(gen), pb.ptr, pc.ptr)
+            # pa's and pb's zero tails are gone: re-zeroing them is part of a repeated composition
+            lib.zkg_arr_op_device(cid, zk.ARR_OP_CODE["set_const"], n, None, None, None, P(zero[0]), P(one),
+                                  pa.ptr + n * 32)
+            lib.zkg_arr_op_device(cid, zk.ARR_OP_CODE["set_const"], n, None, None, None, P(zero[0]), P(one),
+                                  pb.ptr + n * 32)
+        comp = sorted(timeit(composed, reps) for _ in range(rounds))
+        new = sorted(timeit(lambda: lib.zkg_poly_mul_device(cid, n, da.ptr, n, db.ptr, dt.ptr), reps)
+                     for _ in range(rounds))
+        sqr = timeit(lambda: lib.zkg_poly_mul_device(cid, n, da.ptr, n, da.ptr, dt.ptr), reps)
+        short = timeit(lambda: lib.zkg_poly_mul_device(cid, n, da.ptr, 2, db.ptr, dt.ptr), reps)
+        res["product"][f"2^{lg}"] = {
+            "balanced_ms": new[rounds // 2] * 1e3, "balanced_ms_min_max": [new[0] * 1e3, new[-1] * 1e3],
+            "composed_ms": comp[rounds // 2] * 1e3, "composed_ms_min_max": [comp[0] * 1e3, comp[-1] * 1e3],
+            "composed_spread_ms": (comp[-1] - comp[0]) * 1e3, "square_ms": sqr * 1e3, "long_x2_ms": short * 1e3,
+            "long_x2_roofline": hbm(64 * n, short)}
+        for d in (da, db, dt, pa, pb, pc):
+            d.free()
+    x = zk.gen_fr(CURVE, 5, 1)[0]
+    out4 = np.zeros(4, np.uint64)
+    for lg in (16, 20) if quick else (20, 24):
+        n = 1 << lg
+        a = zk.gen_fr(CURVE, 6, n)
+        da, dp = zk.DeviceBuffer(a), zk.DeviceBuffer.empty(n * 32)
+
+        def composed():
+            lib.zkg_arr_powers_device(cid, n, P(one), P(x), dp.ptr)
+            lib.zkg_arr_dot_device(cid, n, da.ptr, dp.ptr, P(out4))
+        comp = sorted(timeit(composed, reps) for _ in range(rounds))
+        pw = timeit(lambda: lib.zkg_arr_powers_device(cid, n, P(one), P(x), dp.ptr), reps)
+        new = sorted(timeit(lambda: lib.zkg_poly_eval_device(cid, n, da.ptr, P(x), P(out4)), reps)
+                     for _ in range(rounds))
+        res["eval_at"][f"2^{lg}"] = {"ms": new[rounds // 2] * 1e3, "ms_min_max": [new[0] * 1e3, new[-1] * 1e3],
+                                     "roofline": hbm(32 * n, new[rounds // 2]),
+                                     "powers_plus_dot_ms": comp[rounds // 2] * 1e3,
+                                     "powers_plus_dot_ms_min_max": [comp[0] * 1e3, comp[-1] * 1e3],
+                                     "powers_ms": pw * 1e3}
+        da.free()
+        dp.free()
+    n, K = 1 << (16 if quick else 20), 8
+    bufs = [zk.DeviceBuffer(zk.gen_fr(CURVE, 10 + k, n)) for k in range(K)]
+    dt = zk.DeviceBuffer.empty(n * 32)
+    ks = zk.gen_fr(CURVE, 7, K)
+    sec = timeit(lambda: zk.poly_lincomb_device(CURVE, [n] * K, ks, bufs, dt), reps)
+    res["lincomb_K8"] = {"n": n, "ms": sec * 1e3, "roofline": hbm(32 * n * (K + 1), sec)}
+    for d in bufs + [dt]:
+        d.free()
+    if ref:  # one host core, the reference's own C
+        n = 1 << 12
+        a, b, o = zk.gen_fr(CURVE, 3, n), zk.gen_fr(CURVE, 4, n), np.zeros((2 * n - 1, 4), np.uint64)
+        res["cpu_reference"] = {"cores": 1, "mul_naive_2^12x2^12_s": cpu_time(
+            lambda: ref.arr(CURVE, "poly_mont_mul_naive", n, a, n, b, o))}
+        n = 1 << 20
+        a = zk.gen_fr(CURVE, 6, n)
+        res["cpu_reference"]["eval_at_2^20_s"] = cpu_time(lambda: ref.arr(CURVE, "poly_mont_eval_at", n, a, x, out4))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--poly-only", action="store_true", help="only the polynomial-layer lines")
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--g2ext-only", action="store_true", help="only the G2 batch conversion / msmProj lines")
     args = ap.parse_args()
@@ -110,6 +195,9 @@ def main():
     out = {"curve": CURVE, "data": "synthetic (zk_gen.cpp generator; G2 points from the reference's generator)"}
     lib = zk.load()
     P = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    if args.poly_only:
+        print(json.dumps({"poly": poly_rows(ref, args.quick)}), flush=True)
+        return
     if args.g2ext_only:
         if not ref:
             sys.exit("the G2 lines need the reference build (oracle/_ref) for their inputs")
@@ -263,6 +351,7 @@ def main():
             dpt.free()
     if ref:
         out["g2_batch_to_affine"] = g2ext(ref, args.quick)
+    out["poly"] = poly_rows(ref, args.quick)
     print(json.dumps(out), flush=True)
 
 

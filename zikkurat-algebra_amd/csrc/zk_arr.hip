@@ -1114,8 +1114,43 @@ static int div_vanishing_t(Device &dev, int n1, const uint64_t *src, int n, cons
   return *h ? 0 : 1;
 }
 
+template <class Cfg>
+static int poly_degree_t(Device &dev, int n, const uint64_t *a, bool host_io) {
+  hipStream_t st = dev.stream;
+  const size_t N = (size_t)(n > 0 ? n : 0);
+  if (!N) return -1;  // poly_mont.c:26-32
+  dev.arena.reserve((host_io ? N * 32 : 0) + (1 << 20));
+  dev.arena.reset();
+  Stage sg(dev, host_io);
+  const uint64_t *da = sg.in(a, N);
+  int *ddeg = dev.arena.take<int>(1);
+  ZK_CHECK(hipMemsetAsync(ddeg, 0xff, 4, st));  // -1
+  hipLaunchKernelGGL(k_degree, dim3((unsigned)std::min<size_t>(DEG_GRID, (N + DEG_CHUNK - 1) / DEG_CHUNK)), dim3(256), 0, st,
+                     n, da, ddeg);
+  ZK_CHECK(hipGetLastError());
+  int *hdeg = reinterpret_cast<int *>(dev.host_staging(4));
+  ZK_CHECK(hipMemcpyAsync(hdeg, ddeg, 4, hipMemcpyDeviceToHost, st));
+  ZK_CHECK(hipStreamSynchronize(st));
+  return *hdeg;
+}
+
 // ---------------------------------------------------------------------------- public
 
+void arr_mul_enqueue(Device &dev, int curve, size_t n, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_tgt) {
+  ArrArgs g = {};
+  g.op = ARR_MUL;
+  g.n = (int)n;
+  g.a = d_a;
+  g.b = d_b;
+  g.tgt = d_tgt;
+  if (curve == 0) launch_arr_op<BN_Fr>(ARR_MUL, g, dim3(stream_grid(n, true)), dev.stream);
+  else launch_arr_op<BLS_Fr>(ARR_MUL, g, dim3(stream_grid(n, true)), dev.stream);
+}
+int poly_degree(int curve, int n, const uint64_t *a, bool host_io) {
+  Device &dev = current_device();
+  std::lock_guard<std::mutex> lock(dev.mu);
+  return curve == 0 ? poly_degree_t<CfgBN>(dev, n, a, host_io) : poly_degree_t<CfgBLS>(dev, n, a, host_io);
+}
 void arr_op(int curve, int op, int n, const uint64_t *a, const uint64_t *b, const uint64_t *c, const uint64_t *kA,
             const uint64_t *kB, uint64_t *tgt, bool host_io) {
   ZK_REQUIRE(op >= 0 && op < ARR_NUM_OPS, "arr_op: unknown operation");

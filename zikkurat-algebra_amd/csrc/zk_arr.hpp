@@ -43,5 +43,11 @@ void arr_powers(int curve, int n, const uint64_t *kA, const uint64_t *kB, uint64
 // returns 1 if the remainder is zero (quot_by_vanishing); rem may be null
 int poly_div_by_vanishing(int curve, int n1, const uint64_t *src, int expo_n, const uint64_t *eta, int nquot,
                           uint64_t *quot, int nrem, uint64_t *rem, bool host_io);
+// degree of a[0, n) (-1: the zero polynomial or n <= 0), <C>_poly_mont_degree (poly_mont.c:26-32)
+int poly_degree(int curve, int n, const uint64_t *a, bool host_io);
+struct Device;
+// d_tgt = d_a * d_b element-wise on DEVICE buffers, enqueued on dev.stream without touching the
+// arena and without waiting (caller holds dev.mu; n < 2^31): the pointwise step of zk_poly.hip
+void arr_mul_enqueue(Device &dev, int curve, size_t n, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_tgt);
 
 }  // namespace zk

@@ -149,6 +149,102 @@ ZKG_API int zkg_poly_div_by_vanishing_device(int curve, int n1, const uint64_t *
 
 }  // extern "C"
 
+// ---------------------------------------------------------------------------- polynomial layer
+// <C>_poly_mont_{degree,is_zero,is_equal,neg,add,sub,scale,lincomb,mul_naive,eval_at}
+//   lib/cbits/curves/poly/mont/bls12_381_poly_mont.c:26-243, bound by Poly.hs:199-209.
+// add / sub / neg / scale / is_zero / is_equal are the Fr vector ops above on the common prefix and
+// the tail; the product, the evaluation and the linear combination are zk_poly.hip.
+#include <vector>
+#include "zk_poly.hpp"
+
+namespace {
+inline int nn(int n) { return n > 0 ? n : 0; }
+// tgt[0, max) = a (+|-) b: the op on the common prefix, then the longer operand's tail copied
+// (src1's, or src2's for add) or negated (src2's for sub), poly_mont.c:95-143
+void poly_addsub_g(int curve, bool sub, int n1, const uint64_t *a, int n2, const uint64_t *b, uint64_t *t) {
+  n1 = nn(n1);
+  n2 = nn(n2);
+  const int M = n1 < n2 ? n1 : n2;
+  const size_t off = 4 * (size_t)M;
+  arr_op_g(curve, sub ? ARR_SUB : ARR_ADD, M, a, b, 0, 0, 0, t, true);
+  if (n1 > M) arr_op_g(curve, ARR_COPY, n1 - M, a + off, 0, 0, 0, 0, t + off, true);
+  else if (n2 > M) arr_op_g(curve, sub ? ARR_NEG : ARR_COPY, n2 - M, b + off, 0, 0, 0, 0, t + off, true);
+}
+uint8_t poly_is_equal_g(int curve, int n1, const uint64_t *a, int n2, const uint64_t *b) {
+  n1 = nn(n1);
+  n2 = nn(n2);
+  const int M = n1 < n2 ? n1 : n2;
+  if (!arr_pred_g(curve, PRED_IS_EQUAL, M, a, b, true)) return 0;
+  if (n1 > M) return (uint8_t)arr_pred_g(curve, PRED_IS_ZERO, n1 - M, a + 4 * (size_t)M, nullptr, true);
+  if (n2 > M) return (uint8_t)arr_pred_g(curve, PRED_IS_ZERO, n2 - M, b + 4 * (size_t)M, nullptr, true);
+  return 1;
+}
+void poly_mul_g(int curve, int n1, const uint64_t *a, int n2, const uint64_t *b, uint64_t *t) {
+  guard([&] {
+    ZK_REQUIRE(zk::poly_mul(curve, n1, a, n2, b, t, true) == 0,
+               "poly_mul: n1 + n2 - 1 exceeds the largest transform of this curve");
+  });
+}
+void poly_lincomb_g(int curve, int K, const int *ns, const uint64_t **coeffs, const uint64_t **polys, uint64_t *t) {
+  guard([&] {
+    std::vector<uint64_t> c((size_t)nn(K) * 4);
+    for (int k = 0; k < K; k++) memcpy(&c[(size_t)k * 4], coeffs[k], 32);
+    zk::poly_lincomb(curve, K, ns, c.data(), polys, t, true);
+  });
+}
+}  // namespace
+
+extern "C" {
+
+#define ZKG_POLY_ENTRIES(PFX, CID)                                                                                  \
+  ZKG_API int PFX##_poly_mont_degree(int n1, const uint64_t *s) {                                                   \
+    return guard_ret(-1, [&] { return zk::poly_degree(CID, n1, s, true); });                                        \
+  }                                                                                                                 \
+  ZKG_API uint8_t PFX##_poly_mont_is_zero(int n1, const uint64_t *s) {                                              \
+    return (uint8_t)arr_pred_g(CID, PRED_IS_ZERO, nn(n1), s, nullptr, true);                                        \
+  }                                                                                                                 \
+  ZKG_API uint8_t PFX##_poly_mont_is_equal(int n1, const uint64_t *a, int n2, const uint64_t *b) {                  \
+    return poly_is_equal_g(CID, n1, a, n2, b);                                                                      \
+  }                                                                                                                 \
+  ZKG_API void PFX##_poly_mont_neg(int n1, const uint64_t *s, uint64_t *t) { arr_op_g(CID, ARR_NEG, nn(n1), s, 0, 0, 0, 0, t, true); } \
+  ZKG_API void PFX##_poly_mont_add(int n1, const uint64_t *a, int n2, const uint64_t *b, uint64_t *t) {             \
+    poly_addsub_g(CID, false, n1, a, n2, b, t);                                                                     \
+  }                                                                                                                 \
+  ZKG_API void PFX##_poly_mont_sub(int n1, const uint64_t *a, int n2, const uint64_t *b, uint64_t *t) {             \
+    poly_addsub_g(CID, true, n1, a, n2, b, t);                                                                      \
+  }                                                                                                                 \
+  ZKG_API void PFX##_poly_mont_scale(const uint64_t *k, int n2, const uint64_t *s, uint64_t *t) {                   \
+    arr_op_g(CID, ARR_SCALE, nn(n2), s, 0, 0, k, 0, t, true);                                                       \
+  }                                                                                                                 \
+  ZKG_API void PFX##_poly_mont_lincomb(int K, const int *ns, const uint64_t **coeffs, const uint64_t **polys,       \
+                                       uint64_t *t) {                                                               \
+    poly_lincomb_g(CID, K, ns, coeffs, polys, t);                                                                   \
+  }                                                                                                                 \
+  ZKG_API void PFX##_poly_mont_mul_naive(int n1, const uint64_t *a, int n2, const uint64_t *b, uint64_t *t) {       \
+    poly_mul_g(CID, n1, a, n2, b, t);                                                                               \
+  }                                                                                                                 \
+  ZKG_API void PFX##_poly_mont_eval_at(int n1, const uint64_t *s, const uint64_t *loc, uint64_t *t) {               \
+    guard([&] { zk::poly_eval(CID, n1, s, loc, t, true); });                                                        \
+  }
+
+ZKG_POLY_ENTRIES(bn128, ZKG_BN128)
+ZKG_POLY_ENTRIES(bls12_381, ZKG_BLS12_381)
+
+ZKG_API int zkg_poly_mul_device(int curve, int n1, const uint64_t *d_a, int n2, const uint64_t *d_b, uint64_t *d_tgt) {
+  return guard_ret(-1, [&] { return zk::poly_mul(curve, n1, d_a, n2, d_b, d_tgt, false); });
+}
+ZKG_API void zkg_poly_eval_device(int curve, int n, const uint64_t *d_poly, const uint64_t *x, uint64_t *tgt) {
+  guard([&] { zk::poly_eval(curve, n, d_poly, x, tgt, false); });
+}
+ZKG_API void zkg_poly_lincomb_device(int curve, int K, const int *ns, const uint64_t *coeffs,
+                                     const uint64_t *const *d_polys, uint64_t *d_tgt) {
+  guard([&] { zk::poly_lincomb(curve, K, ns, coeffs, d_polys, d_tgt, false); });
+}
+ZKG_API void zkg_poly_set_mul_direct_max(int len) { zk::poly_set_mul_direct_max(len); }
+ZKG_API int zkg_poly_last_mul_path(void) { return zk::poly_last_mul_path(); }
+
+}  // extern "C"
+
 // ---------------------------------------------------------------------------- G1
 #include "zk_g1ext.hpp"
 

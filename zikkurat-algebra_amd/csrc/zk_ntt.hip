@@ -691,6 +691,64 @@ static void spread_out(Device &dev0, const Spread &sp, uint64_t *h, const uint64
   ZK_CHECK(hipSetDevice(dev0.id));
 }
 
+// the pass chain of one transform on device buffers: d_src -> d_dst through `scratch` (N elements;
+// the three buffers are distinct), enqueued on dev.stream (caller holds dev.mu)
+template <class Cfg>
+static void ntt_passes(Device &dev, int m, const std::vector<int> &dig, const TwSet &tw, const uint64_t *d_src,
+                       uint64_t *d_dst, uint64_t *scratch, bool timed) {
+  using F = typename Cfg::Fd;
+  const size_t N = (size_t)1 << m;
+  const int P = (int)dig.size();
+  size_t S = N, T = 1;
+  const uint64_t *in = d_src;
+  hipStream_t st = dev.stream;
+  PassArgs pa;
+  pa.m = m;
+  pa.P = P;
+  for (int p = 0; p < P && p < 8; p++) pa.dig[p] = dig[p];
+  for (int p = 0; p < P; p++) {
+    const int r = dig[p];
+    const int R = 1 << r;
+    S >>= r;
+    const int last = (p == P - 1);
+    uint64_t *out = last ? d_dst : scratch;
+    const bool big = r > 8;  // 2^9..2^12-point DFTs: 1024 threads over 4096-element tiles
+    const int tile = big ? NTT_TILE_BIG : NTT_TILE;
+    int G;
+    if (P == 1) {
+      G = 1;
+    } else if (!last) {
+      G = tile / R;
+      if ((size_t)G > S) G = (int)S;
+    } else {
+      G = tile / R;
+      if (G > (1 << dig[0])) G = 1 << dig[0];
+    }
+    const size_t ntiles = N / ((size_t)R * G);
+    const size_t lds = (size_t)G * R * F::N * 4;
+    pa.r = r;
+    pa.S = (int)S;
+    pa.T = (int)T;
+    pa.last = last;
+    pa.G = G;
+    pa.h = tw.h;
+    pa.otf = (!last && !tw.tab[p]) ? 1 : 0;
+    const void *kfn = big ? (const void *)k_ntt_pass<F, NTT_THREADS_BIG> : (const void *)k_ntt_pass<F, NTT_THREADS>;
+    ZK_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (p == 0 && timed) timer_begin(dev);
+    if (big)
+      hipLaunchKernelGGL((k_ntt_pass<F, NTT_THREADS_BIG>), dim3((unsigned)ntiles), dim3(NTT_THREADS_BIG), lds, st, in,
+                         out, pa, tw.inner_i[p], tw.tab[p], last ? tw.scale : nullptr, tw.tlo, tw.thi);
+    else
+      hipLaunchKernelGGL((k_ntt_pass<F, NTT_THREADS>), dim3((unsigned)ntiles), dim3(NTT_THREADS), lds, st, in, out,
+                         pa, tw.inner_i[p], tw.tab[p], last ? tw.scale : nullptr, tw.tlo, tw.thi);
+    ZK_CHECK(hipGetLastError());
+    if (last && timed) timer_end(dev);
+    in = out;
+    T <<= r;
+  }
+}
+
 template <class Cfg>
 static void ntt_run(Device &dev, int curve, int m, const uint64_t *gen_mont, const uint64_t *src, uint64_t *dst,
                     bool host_io, bool inverse, const Spread *sp = nullptr) {
@@ -699,7 +757,6 @@ static void ntt_run(Device &dev, int curve, int m, const uint64_t *gen_mont, con
   hipStream_t st = dev.stream;
   std::vector<int> dig;
   split_digits(m, dig);
-  const int P = (int)dig.size();
   TwSet &tw = twiddles<Cfg>(dev, curve, m, gen_mont, inverse, dig);
 
   const size_t elbytes = (size_t)F::N64 * 8;
@@ -745,54 +802,7 @@ static void ntt_run(Device &dev, int curve, int m, const uint64_t *gen_mont, con
     }
   }
   uint64_t *scratch = dev.arena.take<uint64_t>(N * F::N64);
-
-  size_t S = N, T = 1;
-  const uint64_t *in = d_src;
-  PassArgs pa;
-  pa.m = m;
-  pa.P = P;
-  for (int p = 0; p < P && p < 8; p++) pa.dig[p] = dig[p];
-  for (int p = 0; p < P; p++) {
-    const int r = dig[p];
-    const int R = 1 << r;
-    S >>= r;
-    const int last = (p == P - 1);
-    uint64_t *out = last ? d_dst : scratch;
-    const bool big = r > 8;  // 2^9..2^12-point DFTs: 1024 threads over 4096-element tiles
-    const int tile = big ? NTT_TILE_BIG : NTT_TILE;
-    int G;
-    if (P == 1) {
-      G = 1;
-    } else if (!last) {
-      G = tile / R;
-      if ((size_t)G > S) G = (int)S;
-    } else {
-      G = tile / R;
-      if (G > (1 << dig[0])) G = 1 << dig[0];
-    }
-    const size_t ntiles = N / ((size_t)R * G);
-    const size_t lds = (size_t)G * R * F::N * 4;
-    pa.r = r;
-    pa.S = (int)S;
-    pa.T = (int)T;
-    pa.last = last;
-    pa.G = G;
-    pa.h = tw.h;
-    pa.otf = (!last && !tw.tab[p]) ? 1 : 0;
-    const void *kfn = big ? (const void *)k_ntt_pass<F, NTT_THREADS_BIG> : (const void *)k_ntt_pass<F, NTT_THREADS>;
-    ZK_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (p == 0) timer_begin(dev);
-    if (big)
-      hipLaunchKernelGGL((k_ntt_pass<F, NTT_THREADS_BIG>), dim3((unsigned)ntiles), dim3(NTT_THREADS_BIG), lds, st, in,
-                         out, pa, tw.inner_i[p], tw.tab[p], last ? tw.scale : nullptr, tw.tlo, tw.thi);
-    else
-      hipLaunchKernelGGL((k_ntt_pass<F, NTT_THREADS>), dim3((unsigned)ntiles), dim3(NTT_THREADS), lds, st, in, out,
-                         pa, tw.inner_i[p], tw.tab[p], last ? tw.scale : nullptr, tw.tlo, tw.thi);
-    ZK_CHECK(hipGetLastError());
-    if (last) timer_end(dev);
-    in = out;
-    T <<= r;
-  }
+  ntt_passes<Cfg>(dev, m, dig, tw, d_src, d_dst, scratch, true);
   if (host_io) {
     if (sp) {
       stream_wait(dev, st);
@@ -803,6 +813,15 @@ static void ntt_run(Device &dev, int curve, int m, const uint64_t *gen_mont, con
   }
   stream_wait(dev, st);
   timer_collect(dev);
+}
+
+void ntt_enqueue(Device &dev, int curve, int m, const uint64_t *gen_mont, const uint64_t *d_src, uint64_t *d_dst,
+                 uint64_t *scratch, bool inverse) {
+  ZK_REQUIRE(m >= 0 && m <= 30, "ntt: log2 size out of range (0..30)");
+  std::vector<int> dig;
+  split_digits(m, dig);
+  if (curve == 0) ntt_passes<CfgBN>(dev, m, dig, twiddles<CfgBN>(dev, curve, m, gen_mont, inverse, dig), d_src, d_dst, scratch, false);
+  else ntt_passes<CfgBLS>(dev, m, dig, twiddles<CfgBLS>(dev, curve, m, gen_mont, inverse, dig), d_src, d_dst, scratch, false);
 }
 
 void ntt_release(Device &dev) {

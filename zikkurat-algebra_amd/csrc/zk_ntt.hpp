@@ -15,6 +15,11 @@ void ntt_set_max_radix(int r);
 // reading a cached table (default 2^25; 0 restores it)
 void ntt_set_table_max(size_t entries);
 struct Device;
+// one transform between DEVICE buffers, enqueued on dev.stream without touching the arena and
+// without waiting (caller holds dev.mu): d_src -> d_dst through `scratch`, three distinct buffers
+// of 2^m elements.  The polynomial product (zk_poly.hip) runs its transforms through this.
+void ntt_enqueue(Device &dev, int curve, int m, const uint64_t *gen_mont, const uint64_t *d_src, uint64_t *d_dst,
+                 uint64_t *scratch, bool inverse);
 // frees every cached twiddle table of this context (caller holds dev.mu)
 void ntt_release(Device &dev);
 }  // namespace zk

@@ -69,6 +69,13 @@ EXTENSION_SYMBOLS = [
     "zkg_g1_msm_device_sharded", "zkg_set_error_mode", "zkg_last_error", "zkg_g2_batch_to_affine_device",
 ]
 
+# polynomial layer (lib/cbits/curves/poly/mont/<C>_poly_mont.c:26-243)
+POLY_OPS = ["degree", "is_zero", "is_equal", "neg", "add", "sub", "scale", "lincomb", "mul_naive", "eval_at"]
+REFERENCE_SYMBOLS += [f"{c}_poly_mont_{o}" for c in CURVES for o in POLY_OPS]
+EXTENSION_SYMBOLS += ["zkg_poly_mul_device", "zkg_poly_eval_device", "zkg_poly_lincomb_device",
+                      "zkg_poly_set_mul_direct_max", "zkg_poly_last_mul_path"]
+POLY_MUL_MAX_LOG = {"bn128": 28, "bls12_381": 30}   # largest product, log2 of n1 + n2 - 1
+
 _lib = None
 
 
@@ -105,6 +112,15 @@ def load():
             for o in ("is_valid", "is_zero", "is_one", "is_equal"):
                 getattr(lib, f"{c}_arr_mont_{o}").restype = ctypes.c_uint8
             getattr(lib, f"{c}_poly_mont_quot_by_vanishing").restype = ctypes.c_uint8
+            for o in ("is_zero", "is_equal"):
+                getattr(lib, f"{c}_poly_mont_{o}").restype = ctypes.c_uint8
+            getattr(lib, f"{c}_poly_mont_lincomb").argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                                                ctypes.POINTER(U64P), ctypes.POINTER(U64P), U64P]
+        lib.zkg_poly_mul_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_void_p]
+        lib.zkg_poly_eval_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, U64P, U64P]
+        lib.zkg_poly_lincomb_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), U64P,
+                                                ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]
         lib.zkg_arr_op_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, U64P, U64P, ctypes.c_void_p]
         lib.zkg_arr_dot_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, U64P]
@@ -586,6 +602,100 @@ def quot_by_vanishing(curve, poly, expo_n, eta):
     return q if ok else None
 
 
+# ----------------------------------------------------------------------------- polynomials (Poly.hs)
+
+def _poly(curve, op):
+    require_gpu()
+    return getattr(load(), f"{curve}_poly_mont_{op}")
+
+
+def _k(x):
+    x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1)
+    if x.shape[0] != NLIMBS_R:
+        raise TypeError("an Fr element has 4 words")
+    return x
+
+
+def poly_mul(curve, a, b):
+    """Poly (*) (Poly.hs:133 binds it to mul_naive): the n1 + n2 - 1 coefficients of a * b, by the
+    direct kernel (short factor) or by NTTs; bit-identical to the reference's double loop.  An empty
+    factor gives what the reference's loop writes: max(0, n1 + n2 - 1) zeros."""
+    a, b = _fr(a), _fr(b)
+    n = a.shape[0] + b.shape[0] - 1
+    if n > (1 << POLY_MUL_MAX_LOG[curve]):
+        raise ValueError(f"poly_mul: more than 2^{POLY_MUL_MAX_LOG[curve]} coefficients")
+    out = np.zeros((max(0, n), 4), dtype=np.uint64)
+    _poly(curve, "mul_naive")(a.shape[0], _p(a), b.shape[0], _p(b), _p(out))
+    return out
+
+
+def poly_sqr(curve, a):
+    """Poly sqr x = mul x x: the same array as both factors (one forward transform)"""
+    a = _fr(a)
+    return poly_mul(curve, a, a)
+
+
+def poly_eval_at(curve, poly, x):
+    """Poly.evalAt (Poly.hs:229-237)"""
+    poly = _fr(poly)
+    out = np.zeros(4, dtype=np.uint64)
+    _poly(curve, "eval_at")(poly.shape[0], _p(poly), _p(_k(x)), _p(out))
+    return out
+
+
+def _poly_binary(curve, op, a, b):
+    a, b = _fr(a), _fr(b)
+    out = np.zeros((max(a.shape[0], b.shape[0]), 4), dtype=np.uint64)
+    _poly(curve, op)(a.shape[0], _p(a), b.shape[0], _p(b), _p(out))
+    return out
+
+
+def poly_add(curve, a, b): return _poly_binary(curve, "add", a, b)
+def poly_sub(curve, a, b): return _poly_binary(curve, "sub", a, b)
+
+
+def poly_neg(curve, a):
+    a = _fr(a)
+    out = np.zeros_like(a)
+    _poly(curve, "neg")(a.shape[0], _p(a), _p(out))
+    return out
+
+
+def poly_scale(curve, k, a):
+    a = _fr(a)
+    out = np.zeros_like(a)
+    _poly(curve, "scale")(_p(_k(k)), a.shape[0], _p(a), _p(out))
+    return out
+
+
+def poly_lincomb(curve, terms):
+    """sum of k_i * p_i over terms = [(k_i, p_i), ...]; max length of the p_i coefficients"""
+    ks = [_k(k) for k, _ in terms]
+    ps = [_fr(p) for _, p in terms]
+    K = len(terms)
+    out = np.zeros((max([p.shape[0] for p in ps], default=0), 4), dtype=np.uint64)
+    ns = (ctypes.c_int * max(1, K))(*[p.shape[0] for p in ps])
+    cs = (U64P * max(1, K))(*[_p(k) for k in ks])
+    pp = (U64P * max(1, K))(*[_p(p) for p in ps])
+    _poly(curve, "lincomb")(K, ns, cs, pp, _p(out))
+    return out
+
+
+def poly_is_zero(curve, a):
+    a = _fr(a)
+    return bool(_poly(curve, "is_zero")(a.shape[0], _p(a)))
+
+
+def poly_is_equal(curve, a, b):
+    a, b = _fr(a), _fr(b)
+    return bool(_poly(curve, "is_equal")(a.shape[0], _p(a), b.shape[0], _p(b)))
+
+
+def poly_degree(curve, a):
+    a = _fr(a)
+    return int(_poly(curve, "degree")(a.shape[0], _p(a)))
+
+
 ARR_OP_CODE = {"neg": 0, "add": 1, "sub": 2, "sub_rev": 3, "sqr": 4, "mul": 5, "mul_add": 6, "mul_sub": 7,
                "scale": 8, "Ax_plus_y": 9, "Ax_plus_By": 10, "from_std": 11, "to_std": 12, "copy": 13,
                "set_const": 14, "inv": 15, "div": 16}
@@ -672,6 +782,37 @@ def arr_op_device(curve, op, n, d_a, d_b=None, d_c=None, kA=None, kB=None, d_tgt
     kb = np.ascontiguousarray(kB if kB is not None else z, dtype=np.uint64)
     load().zkg_arr_op_device(CURVE_ID[curve], ARR_OP_CODE[op], n, d_a.ptr if d_a else None,
                              d_b.ptr if d_b else None, d_c.ptr if d_c else None, _p(ka), _p(kb), d_tgt.ptr)
+
+
+def poly_mul_device(curve, n1, d_a, n2, d_b, d_tgt):
+    """device-resident product (zkg_poly_mul_device): 0, or -1 when n1 + n2 - 1 is too large; d_a may be d_b"""
+    return load().zkg_poly_mul_device(CURVE_ID[curve], n1, d_a.ptr if d_a else None, n2, d_b.ptr if d_b else None,
+                                      d_tgt.ptr if d_tgt else None)
+
+
+def poly_eval_device(curve, n, d_poly, x):
+    out = np.zeros(4, dtype=np.uint64)
+    load().zkg_poly_eval_device(CURVE_ID[curve], n, d_poly.ptr if d_poly else None, _p(_k(x)), _p(out))
+    return out
+
+
+def poly_lincomb_device(curve, ns, coeffs, d_polys, d_tgt):
+    """d_tgt = sum_k coeffs[k] * d_polys[k][:ns[k]] (zkg_poly_lincomb_device); coeffs: (K, 4) host array"""
+    K = len(ns)
+    cs = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(max(K, 0), 4) if K else np.zeros((1, 4), np.uint64)
+    cn = (ctypes.c_int * max(1, K))(*ns)
+    pp = (ctypes.c_void_p * max(1, K))(*[d.ptr for d in d_polys])
+    load().zkg_poly_lincomb_device(CURVE_ID[curve], K, cn, _p(cs), pp, d_tgt.ptr if d_tgt else None)
+
+
+def poly_set_mul_direct_max(length):
+    """test hook: shorter factor <= length takes the direct kernel (0: always the NTT, < 0: default)"""
+    load().zkg_poly_set_mul_direct_max(int(length))
+
+
+def poly_last_mul_path():
+    """0: the most recent product ran on the direct kernel; else log2 of its transform size"""
+    return load().zkg_poly_last_mul_path()
 
 
 def ntt_device(curve, m, gen, d_src, d_dst, inverse=False):
