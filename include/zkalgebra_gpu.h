@@ -106,6 +106,18 @@ ZKG_API void bn128_G2_proj_batch_to_affine  ( int N, const uint64_t *src , uint6
 ZKG_API void bls12_381_G2_proj_batch_from_affine( int N, const uint64_t *src , uint64_t *tgt );
 ZKG_API void bls12_381_G2_proj_batch_to_affine  ( int N, const uint64_t *src , uint64_t *tgt );
 
+/* G2 group (curve) FFT (bls12_381_G2_proj.h:48-49, bn128_G2_proj.h same lines; Haskell forwardFFT /
+ * inverseFFT = curveFFT / curveIFFT of the G2 instance, G2/Proj.hs).  Host buffers of 2^m projective
+ * rows (6 NP words), m in 0..24; gen is the Montgomery generator of the order-2^m subgroup of Fr.
+ * Every level multiplies by the integer value of the reference's canonical scalar at that position
+ * (both twists have a cofactor), so the output equals the reference's for every on-curve input.
+ * Outputs are normalised like the reference's (bls12_381_G2_proj.c:70-89, 716-718): (x : y : 1),
+ * infinity (0 : 1 : 0); an input row with Z = 0 is the point at infinity. */
+ZKG_API void bn128_G2_proj_fft_forward( int m, const uint64_t *gen, const uint64_t *src, uint64_t *tgt );
+ZKG_API void bn128_G2_proj_fft_inverse( int m, const uint64_t *gen, const uint64_t *src, uint64_t *tgt );
+ZKG_API void bls12_381_G2_proj_fft_forward( int m, const uint64_t *gen, const uint64_t *src, uint64_t *tgt );
+ZKG_API void bls12_381_G2_proj_fft_inverse( int m, const uint64_t *gen, const uint64_t *src, uint64_t *tgt );
+
 /* G1 batch conversions and the group (curve) FFT.
  *   bls12_381_G1_proj.h:9-10, 48-49 (bn128_G1_proj.h same lines); Haskell batchFromAffine /
  *   batchToAffine (G1/Proj.hs:409-430), forwardFFT / inverseFFT = curveFFT / curveIFFT
@@ -367,6 +379,11 @@ ZKG_API void zkg_g1_jac_fft_device(int curve, int inverse, int m, const uint64_t
 ZKG_API void zkg_g1_jac_batch_to_affine_device(int curve, int n, const uint64_t *d_src, uint64_t *d_tgt);
 /* device-resident G2 batch_to_affine: n projective rows (6 NP words) -> n affine rows (4 NP words) */
 ZKG_API void zkg_g2_batch_to_affine_device(int curve, int n, const uint64_t *d_src, uint64_t *d_tgt);
+/* device-resident G2 group FFT (d_* DEVICE pointers, gen on the host; the <C>_G2_proj_fft_* contract) */
+ZKG_API void zkg_g2_fft_device(int curve, int inverse, int m, const uint64_t *gen, const uint64_t *d_src, uint64_t *d_tgt);
+/* test hook: cap on the scalar-multiplication lanes of a G2 FFT stage (rounded up to 256; 0 restores the default),
+ * so that the grid-stride loop of a stage is exercised at small sizes */
+ZKG_API void zkg_g2_fft_set_max_lanes(int lanes);
 
 /* host helpers on G1 (projective, reference Montgomery form) */
 ZKG_API void zkg_g1_proj_add(int curve, const uint64_t *a, const uint64_t *b, uint64_t *out);

@@ -526,7 +526,7 @@ JAC_X = 10  # Jacobian accumulator / table-entry invariant of the lazy group-FFT
 
 
 def jac_form(F):
-    """zk_g1ext.hip (ZK_FFT_LAZY): X < JAC_X p, Y, Z < 2p, normalised limbs"""
+    """zk_fftdev.hpp (ZK_FFT_LAZY): X < JAC_X p, Y, Z < 2p, normalised limbs"""
     return {"X": F.norm_val(JAC_X * F.p, "X"), "Y": F.norm_val(2 * F.p, "Y"), "Z": F.norm_val(2 * F.p, "Z")}
 
 
@@ -538,7 +538,7 @@ def in_jac_form(F, pt, what):
 
 
 def jac_dbl_lazy(F):
-    """zk_g1ext.hip jac_dbl, ZK_FFT_LAZY (both base fields): dbl-2009-l with the multiples folded into
+    """zk_fftdev.hpp jac_dbl, ZK_FFT_LAZY (both base fields): dbl-2009-l with the multiples folded into
     products and lazy differences; Y3 one shared-reduction pair"""
     tag = "jac_dbl_lazy"
     pt = jac_form(F)
@@ -569,7 +569,7 @@ def jac_dbl_lazy(F):
 
 
 def jac_add_cached_lazy(F):
-    """zk_g1ext.hip jac_add_cached, ZK_FFT_LAZY: add-1998-cmo-2 with the table entry's Z^2, Z^3
+    """zk_fftdev.hpp jac_add_cached, ZK_FFT_LAZY: add-1998-cmo-2 with the table entry's Z^2, Z^3
     cached (products), H and r exact (zero-tested), the rest lazy"""
     tag = "jac_add_cached_lazy"
     acc = jac_form(F)

@@ -309,6 +309,13 @@ extern "C" {
   }                                                                                            \
   ZKG_API void PFX##_G2_proj_batch_to_affine(int N, const uint64_t *src, uint64_t *tgt) {      \
     guard([&] { zk::g2_batch_to_affine(CID, N, src, tgt, true); });                            \
+  }                                                                                            \
+  /* the G2 group FFT (bls12_381_G2_proj.c:670-781; G2/Proj.hs forwardFFT / inverseFFT) */      \
+  ZKG_API void PFX##_G2_proj_fft_forward(int m, const uint64_t *gen, const uint64_t *src, uint64_t *tgt) { \
+    guard([&] { zk::g2_fft(CID, m, gen, src, tgt, true, false); });                            \
+  }                                                                                            \
+  ZKG_API void PFX##_G2_proj_fft_inverse(int m, const uint64_t *gen, const uint64_t *src, uint64_t *tgt) { \
+    guard([&] { zk::g2_fft(CID, m, gen, src, tgt, true, true); });                             \
   }
 
 ZKG_G2EXT_ENTRIES(bn128, ZKG_BN128)
@@ -317,5 +324,10 @@ ZKG_G2EXT_ENTRIES(bls12_381, ZKG_BLS12_381)
 ZKG_API void zkg_g2_batch_to_affine_device(int curve, int n, const uint64_t *d_src, uint64_t *d_tgt) {
   guard([&] { zk::g2_batch_to_affine(curve, n, d_src, d_tgt, false); });
 }
+ZKG_API void zkg_g2_fft_device(int curve, int inverse, int m, const uint64_t *gen, const uint64_t *d_src,
+                               uint64_t *d_tgt) {
+  guard([&] { zk::g2_fft(curve, m, gen, d_src, d_tgt, false, inverse != 0); });
+}
+ZKG_API void zkg_g2_fft_set_max_lanes(int lanes) { zk::g2_fft_set_max_lanes(lanes); }
 
 }  // extern "C"

@@ -53,7 +53,8 @@ REFERENCE_SYMBOLS += [f"{c}_arr_mont_{o}" for c in CURVES for o in ARR_OPS] + [
     for f in ("batch_from_affine", "batch_to_affine", "fft_forward", "fft_inverse")] + [
     f"{c}_G2_proj_MSM_{k}_coeff_{o}_out" for c in CURVES for k in ("mont", "std") for o in ("proj", "affine")] + [
     f"{c}_G2_proj_{f}" for c in CURVES
-    for f in ("batch_from_affine", "batch_to_affine", "MSM_std_coeff_proj_out_variable")]
+    for f in ("batch_from_affine", "batch_to_affine", "MSM_std_coeff_proj_out_variable")] + [
+    f"{c}_G2_proj_fft_{d}" for c in CURVES for d in ("forward", "inverse")]
 EXTENSION_SYMBOLS = [
     "zkg_version", "zkg_device_count", "zkg_set_device", "zkg_device_malloc", "zkg_device_free",
     "zkg_memcpy_htod", "zkg_memcpy_dtoh", "zkg_device_synchronize", "zkg_g1_msm_device", "zkg_ntt_device",
@@ -67,6 +68,7 @@ EXTENSION_SYMBOLS = [
     "zkg_release", "zkg_comm_unique_id", "zkg_comm_init", "zkg_comm_destroy", "zkg_comm_rank", "zkg_comm_world",
     "zkg_comm_allgather", "zkg_comm_barrier", "zkg_comm_max_f64", "zkg_g1_comm_sum_partials",
     "zkg_g1_msm_device_sharded", "zkg_set_error_mode", "zkg_last_error", "zkg_g2_batch_to_affine_device",
+    "zkg_g2_fft_device", "zkg_g2_fft_set_max_lanes",
 ]
 
 # polynomial layer (lib/cbits/curves/poly/mont/<C>_poly_mont.c:26-243)
@@ -98,6 +100,12 @@ def load():
                                        ctypes.c_void_p]
         lib.zkg_g2_msm_device.argtypes = lib.zkg_g1_msm_device.argtypes
         lib.zkg_g2_batch_to_affine_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        lib.zkg_g2_fft_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, U64P, ctypes.c_void_p,
+                                          ctypes.c_void_p]
+        lib.zkg_g2_fft_set_max_lanes.argtypes = [ctypes.c_int]
+        for c in CURVES:
+            for d in ("forward", "inverse"):
+                getattr(lib, f"{c}_G2_proj_fft_{d}").argtypes = [ctypes.c_int, U64P, U64P, U64P]
         lib.zkg_gen_fr.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, U64P]
         lib.zkg_gen_g1_points.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, U64P]
         lib.zkg_timer_read.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
@@ -411,6 +419,40 @@ def inverse_fft(sg, pts, coords="proj"):
 
 curve_fft = forward_fft
 curve_ifft = inverse_fft
+
+
+def _g2_curve_fft(sg, pts, name, msg):
+    pts = np.asarray(pts)
+    if pts.ndim != 2 or pts.shape[1] != 6 * NLIMBS_P[sg.curve]:
+        raise ValueError(f"{name}: G2 rows must be projective, {6 * NLIMBS_P[sg.curve]} limbs")
+    if sg.size != pts.shape[0]:
+        raise ValueError(msg)
+    pts = np.ascontiguousarray(pts, dtype=np.uint64)
+    require_gpu()
+    out = np.zeros_like(pts)
+    getattr(load(), f"{sg.curve}_G2_proj_{name}")(sg.log_size, _p(sg.gen_array()), _p(pts), _p(out))
+    return out
+
+
+def g2_forward_fft(sg, pts):
+    """G2 Proj.forwardFFT = curveFFT (G2/Proj.hs): [L_k(tau)]_2 -> [tau^i]_2, normalised rows"""
+    return _g2_curve_fft(sg, pts, "fft_forward", "forwardNTT: subgroup size differs from the array size")
+
+
+def g2_inverse_fft(sg, pts):
+    """G2 Proj.inverseFFT = curveIFFT (G2/Proj.hs): [tau^i]_2 -> [L_k(tau)]_2, normalised rows"""
+    return _g2_curve_fft(sg, pts, "fft_inverse", "inverseNTT: subgroup size differs from the array size")
+
+
+def g2_fft_device(curve, m, gen, d_src, d_dst, inverse=False):
+    """device-resident G2 group FFT: d_src / d_dst are DeviceBuffers of 2^m projective rows"""
+    load().zkg_g2_fft_device(CURVE_ID[curve], 1 if inverse else 0, m, _p(np.ascontiguousarray(gen, dtype=np.uint64)),
+                             d_src.ptr, d_dst.ptr)
+
+
+def g2_fft_set_max_lanes(lanes):
+    """test hook: cap on the scalar-multiplication lanes of a G2 FFT stage (0 restores the default)"""
+    load().zkg_g2_fft_set_max_lanes(int(lanes))
 
 
 # ----------------------------------------------------------------------------- NTT
