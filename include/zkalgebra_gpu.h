@@ -342,6 +342,22 @@ ZKG_API void zkg_g2_msm_device(int curve, int npoints, const uint64_t *d_expos, 
                                const uint64_t *d_grps, uint64_t *tgt_proj, int window_size);
 /* device-resident NTT: d_src / d_tgt DEVICE pointers; gen on the host */
 ZKG_API void zkg_ntt_device(int curve, int inverse, int m, const uint64_t *gen, const uint64_t *d_src, uint64_t *d_tgt);
+/* batch transforms of 2^m Montgomery Fr each, transform b at row offset b * 2^m.  gen as in
+ * zkg_ntt_device; shift: HOST pointer to one Montgomery Fr, or NULL for the plain transform.
+ *   forward: tgt_b[k] = sum_j src_b[j] * shift^j * gen^(j k)            (= p_b(shift * gen^k))
+ *   inverse: tgt_b[j] = shift^(-j) * (1/N) * sum_k src_b[k] * gen^(-j k)
+ * Outputs canonical.  d_tgt may equal d_src (whole buffer); no partial overlap.
+ * Returns 0; -1 (nothing written) for m outside 0..30, batch < 0, or inverse with shift == 0.
+ * batch == 0 is a no-op.  shift == 0 forward is defined (0^0 = 1: every output is src_b[0]).
+ * Every pass of the whole batch is one launch, and the shift rides on the first pass's load
+ * (forward) or the last pass's closing product (inverse).  When the batch's working set (batch * 2^m
+ * rows of scratch; three times that for the host form) does not fit, it runs in contiguous chunks
+ * of transforms; the result does not depend on the chunking. */
+ZKG_API int zkg_ntt_ext_device(int curve, int inverse, int m, const uint64_t *gen, const uint64_t *shift,
+                               int batch, const uint64_t *d_src, uint64_t *d_tgt);
+/* the same on HOST buffers (calling thread's device; the device set does not spread it) */
+ZKG_API int zkg_ntt_ext(int curve, int inverse, int m, const uint64_t *gen, const uint64_t *shift,
+                        int batch, const uint64_t *src, uint64_t *tgt);
 
 /* device-resident Fr vector ops: d_* are DEVICE pointers, kA/kB and dot's tgt HOST.
  * op codes: 0 neg, 1 add, 2 sub, 3 sub_rev (b - a), 4 sqr, 5 mul, 6 mul_add, 7 mul_sub,
@@ -425,6 +441,9 @@ ZKG_API void zkg_ntt_set_max_radix(int r);
 /* test hook: inter-pass twiddle table entries above which an NTT pass computes its twiddles on
  * the fly (default 2^25, i.e. only transforms of 2^26 and more; 0 restores it) */
 ZKG_API void zkg_ntt_set_table_max(size_t entries);
+/* test hook: blocks per launch of the batched pass kernel of zkg_ntt_ext* (a pass with more tiles
+ * runs as several launches; default and maximum 2^21, 0 restores it) */
+ZKG_API void zkg_ntt_ext_set_max_grid(unsigned tiles);
 /* test hook: device bytes one working-set arena may hold (0: unlimited), to exercise the
  * out-of-memory degrade path (smaller MSM window groups) */
 ZKG_API void zkg_arena_set_limit(size_t bytes);

@@ -37,7 +37,9 @@ invariants they document taken as inputs and re-checked on their outputs:
                   round, radix-4 rounds, odd radix-2 stage), the inter-pass twiddle product
                   (table, and the on-the-fly path, whose twiddle is a product < 1.02p), the last pass's closing step
                   (fe_reduce_small, or the product by 1/N), the packed non-canonical store,
-                  for BN254 Fr and BLS12-381 Fr
+                  for BN254 Fr and BLS12-381 Fr; the coset shift of the batched pass kernel
+                  (ntt_ext_paths, run_ext: the shifted input's canonicalisation, the inverse
+                  shift's closing product)
   * zk_msm_impl.hpp  the scalar REDC (fe_ref_to_std of any 256-bit pattern)
 
 Reference semantics these bounds protect: canonical Montgomery results of the reference's
@@ -515,6 +517,59 @@ def ntt_paths(F):
                  ", ".join(f"2^{r}: {worst[r] / p:.1f}" for r in range(13)) + f"; R'/p = {F.Rp / p:.1f}")
 
 
+NTT_MAX_RADIX_LOG = 12     # zk_ntt.hip NTT_TILE_BIG = 2^12 elements: the largest DFT one pass runs
+NTT_ONE_PASS_MAX_LOG = 11  # zk_ntt.hip split_digits: transforms up to 2^11 points are one pass
+NTT_DFT_SUB = (4, 2)       # zk_ntt.hip lds_dft: the one fe_sub_lazy with a borrow of 2 (K, BW)
+
+
+def ntt_fixed_point(F):
+    """the bound V on the packed values between passes: f(V) <= V for f(V) = max_r (dft_r(V) w / R' + p)
+    over every radix and the larger twiddle bound (tw2's product); as computed in ntt_paths"""
+    p = F.p
+    tw_otf = F.mul(F.norm_val(p), F.norm_val(p), "tw2")
+    vin = p
+    for _ in range(50):
+        nxt = max(p, max(F.mul(ntt_lds_dft(F, r, F.norm_val(vin)), tw_otf, "inter-pass").val
+                         for r in range(1, NTT_MAX_RADIX_LOG + 1)))
+        if nxt <= vin:
+            return vin
+        vin = -(-nxt // (p // 1024)) * (p // 1024)
+    raise BoundError(f"{F.name}: no inter-pass fixed point")
+
+
+def ntt_ext_paths(F):
+    """zk_ntt.hip k_ntt_pass_ext, the coset shift fused into the batched pass kernel.
+    Forward: pass 0 multiplies the loaded word (any 256-bit pattern, canonical in a valid input) by
+    tw2 of the shift table (a product of two canonical entries) before lds_put.  The product is only
+    known to be < 2p, and lds_dft does NOT take < 2p inputs: the first radix-4 round's
+    a2 = b0 + 4p - s23 (fe_sub_lazy<4, 2>) needs the top limb of s23 = a2 + a3 within the borrowed
+    top limb of 4p, which two inputs at 2p - 1 exceed by one (ntt_lds_dft raises for every r >= 2;
+    the inter-pass values are fine because their bound is the fixed point, < 1.72p).  So the kernel
+    canonicalises the product (fe_canon: needs < 2p, normalised limbs -- checked here) and the DFT
+    of every pass sees what the plain transform sees, which ntt_paths covers.
+    Inverse: the last pass's closing product takes the lazily grown DFT output (inputs canonical for
+    a single pass, below the inter-pass fixed point otherwise) times tw2 of the table of shift^-j,
+    whose low half may carry 1/N (canonical entries either way); the result goes through
+    fe_store_ref, so it must be < 2p -- checked for every radix 2^0 .. 2^12."""
+    p = F.p
+    can = F.norm_val(p, "canonical table entry")
+    sh = F.mul(can, can, "tw2(shift table)")
+    x = F.mul(F.norm_val(1 << 256, "fe_load_ref word"), sh, "x * shift^j")
+    F.canon(x, "shifted input")
+    vin = ntt_fixed_point(F)
+    worst = 0
+    for r in range(0, NTT_MAX_RADIX_LOG + 1):
+        for vb in (p, vin):
+            a = F.norm_val(vb, "ntt input")
+            out = ntt_lds_dft(F, r, a) if r > 0 else a
+            y = F.mul(out, sh, f"ext r={r} closing product by shift^-j [/ N]")
+            F.canon(y, "fe_store_ref")
+            worst = max(worst, y.val)
+    F.log.append(f"ntt ext: shifted input < {F.units(x):.3f} p (canonicalised); inverse-shift closing product "
+                 f"< {worst / p:.3f} p over 2^0..2^{NTT_MAX_RADIX_LOG}-point DFTs")
+    return x.val, worst
+
+
 def scalar_redc(F):
     """zk_msm_impl.hpp DigitStream::load: fe_ref_to_std of any 256-bit pattern (k[8] = 0)"""
     x = V([F.MASK] * 8 + [(1 << 256) - 1 >> 232], 1 << 256, "raw scalar")
@@ -665,6 +720,24 @@ def run_all(verbose=True):
     return ok, results
 
 
+def run_ext(verbose=True):
+    """the coset-shift paths of the batched NTT kernel (kept out of run_all's fixed list)"""
+    ok = True
+    for name in ("bls12_381_fr", "bn254_fr"):
+        F = Field(name)
+        try:
+            ntt_ext_paths(F)
+            status = "ok"
+        except BoundError as e:
+            ok, status = False, f"FAIL {e}"
+        if verbose:
+            for line in F.log:
+                print("   " + line)
+            print(f"{name:14s} {'ntt_ext_paths':22s} {status}")
+    return ok
+
+
 if __name__ == "__main__":
     ok, _ = run_all()
+    ok = run_ext() and ok
     sys.exit(0 if ok else 1)

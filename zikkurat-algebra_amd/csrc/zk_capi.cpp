@@ -224,6 +224,15 @@ ZKG_API void zkg_ntt_device(int curve, int inverse, int m, const uint64_t *gen, 
   guard([&] { zk::ntt(curve, m, gen, d_src, d_tgt, false, inverse != 0); });
 }
 
+ZKG_API int zkg_ntt_ext_device(int curve, int inverse, int m, const uint64_t *gen, const uint64_t *shift, int batch,
+                               const uint64_t *d_src, uint64_t *d_tgt) {
+  return guard_ret<int>(-1, [&] { return zk::ntt_ext(curve, m, gen, shift, batch, d_src, d_tgt, false, inverse != 0); });
+}
+ZKG_API int zkg_ntt_ext(int curve, int inverse, int m, const uint64_t *gen, const uint64_t *shift, int batch,
+                        const uint64_t *src, uint64_t *tgt) {
+  return guard_ret<int>(-1, [&] { return zk::ntt_ext(curve, m, gen, shift, batch, src, tgt, true, inverse != 0); });
+}
+
 }  // extern "C"
 
 template <class C>
@@ -311,6 +320,7 @@ ZKG_API void zkg_msm_set_ahead_min(int lg) { zk::msm_set_ahead_min(lg); }
 ZKG_API void zkg_ntt_set_max_radix(int r) { zk::ntt_set_max_radix(r); }
 
 ZKG_API void zkg_ntt_set_table_max(size_t entries) { zk::ntt_set_table_max(entries); }
+ZKG_API void zkg_ntt_ext_set_max_grid(unsigned tiles) { zk::ntt_ext_set_max_grid(tiles); }
 ZKG_API void zkg_arena_set_limit(size_t bytes) { zk::arena_set_limit(bytes); }
 ZKG_API int zkg_msm_last_groups(void) { return zk::msm_last_groups_read(); }
 ZKG_API size_t zkg_msm_workspace_bytes(int curve, int npoints, int expo_nlimbs, int expos_mont, int host_inputs,

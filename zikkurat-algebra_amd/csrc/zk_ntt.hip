@@ -419,6 +419,187 @@ __global__ void __launch_bounds__(NT) k_ntt_pass(const uint64_t *__restrict__ sr
   }
 }
 
+// What the extended pass kernel (k_ntt_pass_ext) adds to a pass: the batch geometry of the launch
+// and the coset shift.  Block blockIdx.x of the launch is tile (tile0 + blockIdx.x) % ntiles of
+// transform (tile0 + blockIdx.x) / ntiles; transform b lives at row offset b * 2^m of src, dst.
+// slo / shi: two-level power table of the shift (forward) or of its inverse (inverse), laid out as
+// tlo / thi with split sh.
+struct ExtArgs {
+  unsigned long long tile0;  // global tile index of block 0 of this launch
+  unsigned ntiles;           // tiles per transform in this pass
+  int mode;                  // 0: no shift, 1: x_j *= shift^j on load (pass 0), 2: y_j *= shift^-j [/ N] on the last store
+  int sh;
+  const uint64_t *slo, *shi;
+};
+
+// One pass of a whole batch of transforms, with the coset shift fused in (zkg_ntt_ext*): k_ntt_pass's
+// tile geometry, lds_dft and closing modes, and beside them the batch index (the tile and the
+// transform come from ExtArgs), the shift product on the load of pass 0 and the inverse shift as
+// one more closing mode of the last pass.  A kernel of its own, so that k_ntt_pass -- what every
+// single-transform entry point launches -- keeps its source and its registers.
+template <class F, int NT>
+__global__ void __launch_bounds__(NT) k_ntt_pass_ext(const uint64_t *__restrict__ src_all,
+                                                              uint64_t *__restrict__ dst_all, PassArgs a,
+                                                              const uint32_t *__restrict__ itw_i,
+                                                              const uint64_t *__restrict__ tab,
+                                                              const uint64_t *__restrict__ scale,
+                                                              const uint64_t *__restrict__ tlo,
+                                                              const uint64_t *__restrict__ thi, ExtArgs ext) {
+  extern __shared__ uint32_t lds[];
+  constexpr int NW = F::N;
+  const int r = a.r, G = a.G, S = a.S;
+  const int R = 1 << r;
+  uint32_t *data = lds;                          // [G][R] elements
+  const uint32_t *itw = (const uint32_t *)__builtin_assume_aligned(itw_i, 16);  // [R/2] inner twiddles
+  const int tid = threadIdx.x;
+  const unsigned long long gt = ext.tile0 + blockIdx.x;
+  const int tile = (int)(gt % ext.ntiles);
+  const size_t row0 = (size_t)(gt / ext.ntiles) << a.m;  // this transform's rows
+  const uint64_t *__restrict__ src = src_all + row0 * F::N64;
+  uint64_t *__restrict__ dst = dst_all + row0 * F::N64;
+
+  // instance geometry of this tile
+  size_t hi_base = 0;  // non-last: hi * R * S + lo0
+  size_t pos_base = 0, nat_base = 0;  // last: position / natural index of instance k_0 = k0base
+  int k0base = 0, k0stride_pos = 0;
+  if (!a.last) {
+    const int ntl = S / G;
+    hi_base = (size_t)(tile / ntl) * R * S + (size_t)(tile % ntl) * G;
+  } else if (a.P > 1) {
+    const int R0 = 1 << a.dig[0];
+    const int ntile0 = R0 / G;
+    k0base = (tile % ntile0) * G;
+    int rem = tile / ntile0;
+    size_t Sq = (size_t)1 << a.m;
+    size_t Tq = (size_t)R0;
+    for (int q = 0; q < a.P - 1; q++) {
+      Sq >>= a.dig[q];
+      if (q == 0) {
+        k0stride_pos = (int)(Sq >> r);  // position stride of k_0, in units of R
+      } else {
+        const int kq = rem & ((1 << a.dig[q]) - 1);
+        rem >>= a.dig[q];
+        pos_base += (size_t)kq * Sq;
+        nat_base += (size_t)kq * Tq;
+        Tq <<= a.dig[q];
+      }
+    }
+  }
+
+  // load: element (g, k) -> LDS slot g*R + bitrev_r(k)
+  const int nel = G * R;
+  for (int e = tid; e < nel; e += NT) {
+    int g, k;
+    size_t addr;
+    if (!a.last) {
+      g = e % G;
+      k = e / G;
+      addr = hi_base + (size_t)k * S + g;
+    } else {
+      g = e / R;
+      k = e % R;
+      addr = pos_base + ((size_t)(k0base + g) * k0stride_pos) * R + k;
+      if (a.P == 1) addr = k;
+    }
+    Fe<F> x;
+    fe_load_ref(x, src + addr * F::N64);
+    if (ext.mode == 1) {
+      // pass 0 reads natural order: addr is the input index j.  x * shift^j is only < 2p, which
+      // lds_dft's first radix-4 round does not take (its a2 = b0 + 4p - s23 needs s23's top limb
+      // within 4p's borrowed one: tools/lazy_bounds.py ntt_ext_paths), so it is canonicalised and
+      // the DFT sees what a plain transform's pass 0 sees
+      Fe<F> w, y;
+      tw2(w, ext.slo, ext.shi, ext.sh, (uint32_t)addr);
+      fe_mul(y, x, w);
+      fe_canon(y);
+      x = y;
+    }
+    const int kr = r ? (int)(__builtin_bitreverse32((uint32_t)k) >> (32 - r)) : 0;
+    lds_put(data + (size_t)lds_slot((uint32_t)(g * R + kr)) * NW, x);
+  }
+  __syncthreads();
+
+  lds_dft<F, NT>(data, itw, r, G);
+
+  // Output: one loop per closing mode (uniform per launch), so every mode is its own loop in
+  // the ISA (tools/ntt_isa_model.py prices each pass from these loops)
+  //   non-last pass: x * w, w from the pass's table or (otf) tw2; stored packed, not canonical
+  //                  (a product is < 2p < 2^256; the next pass only multiplies and adds it)
+  //   last pass:     the lazily grown value (< 50p) back below 2p, as fe_store_ref's
+  //                  canonicalisation needs -- by the product with the scale (1/N) when an
+  //                  inverse's scale has no table to ride on, else by a product-free reduction
+  auto out_addr = [&](int g, int k) -> size_t {
+    if (!a.last) return hi_base + (size_t)k * S + g;
+    return (a.P == 1) ? (size_t)k : nat_base + (size_t)(k0base + g) + (size_t)k * a.T;
+  };
+  if (!a.last && !a.otf) {
+    for (int e = tid; e < nel; e += NT) {
+      const int g = e % G, k = e / G;  // consecutive threads -> consecutive g (coalesced)
+      Fe<F> x, w, y;
+      lds_get(x, data + (size_t)lds_slot((uint32_t)(g * R + k)) * NW);
+      const size_t addr = out_addr(g, k);
+      fe_load_ref(w, tab + ((size_t)k * S + (addr % S)) * F::N64);
+      fe_mul(y, x, w);
+      fe_store_packed(dst + addr * F::N64, y);
+    }
+  } else if (!a.last) {
+    for (int e = tid; e < nel; e += NT) {
+      const int g = e % G, k = e / G;
+      Fe<F> x, w, y;
+      lds_get(x, data + (size_t)lds_slot((uint32_t)(g * R + k)) * NW);
+      const size_t addr = out_addr(g, k);
+      tw2(w, tlo, thi, a.h, (uint32_t)a.T * (uint32_t)k * (uint32_t)(addr % S));
+      fe_mul(y, x, w);
+      fe_store_packed(dst + addr * F::N64, y);
+    }
+  } else if (ext.mode == 2) {
+    // inverse coset: output j times shift^-j, the table's low half carrying 1/N when this pass owes
+    // it (the host passes no `scale` then); the lazily grown value (< 50p) times tw2's product
+    // (< 1.02p) is < 2p, as fe_store_ref needs
+    for (int e = tid; e < nel; e += NT) {
+      const int g = e % G, k = e / G;
+      Fe<F> x, w, y;
+      lds_get(x, data + (size_t)lds_slot((uint32_t)(g * R + k)) * NW);
+      const size_t addr = out_addr(g, k);
+      tw2(w, ext.slo, ext.shi, ext.sh, (uint32_t)addr);
+      fe_mul(y, x, w);
+      fe_store_ref(dst + addr * F::N64, y);
+    }
+  } else if (scale) {
+    Fe<F> sc, t;
+    fe_load_ref(t, scale);
+    fe_to_int(sc, t);
+    for (int e = tid; e < nel; e += NT) {
+      const int g = e % G, k = e / G;
+      Fe<F> x, y;
+      lds_get(x, data + (size_t)lds_slot((uint32_t)(g * R + k)) * NW);
+      fe_mul(y, x, sc);
+      fe_store_ref(dst + out_addr(g, k) * F::N64, y);
+    }
+  } else {
+    for (int e = tid; e < nel; e += NT) {
+      const int g = e % G, k = e / G;
+      Fe<F> x;
+      lds_get(x, data + (size_t)lds_slot((uint32_t)(g * R + k)) * NW);
+      fe_reduce_small(x);
+      fe_store_ref(dst + out_addr(g, k) * F::N64, x);
+    }
+  }
+}
+
+// shift table: slo[i] *= scale (1/N, reference form), i < n
+template <class F>
+__global__ void k_sh_scale(uint64_t *__restrict__ slo, int n, const uint64_t *__restrict__ scale) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Fe<F> w, s, t, u;
+  fe_load_ref(w, slo + (size_t)i * F::N64);
+  fe_load_ref(s, scale);
+  fe_to_int(t, s);
+  fe_mul(u, w, t);
+  fe_store_ref(slo + (size_t)i * F::N64, u);
+}
+
 // ---------------------------------------------------------------------------- host side
 
 // Pass split.  Default: three-or-more passes of <= 2^8-point DFTs on 1024-element tiles,
@@ -691,6 +872,20 @@ static void spread_out(Device &dev0, const Spread &sp, uint64_t *h, const uint64
   ZK_CHECK(hipSetDevice(dev0.id));
 }
 
+// out of device memory: frees every cached twiddle set of this context but `keep`
+static void drop_other_twiddles(Device &dev, const TwSet &keep) {
+  std::lock_guard<std::mutex> lock(g_tw_mu);
+  ZK_CHECK(hipStreamSynchronize(dev.stream));
+  for (auto it = g_tw.begin(); it != g_tw.end();) {
+    if (std::get<0>(it->first) / 2 == dev.uid && &it->second != &keep) {
+      ZK_CHECK(hipFree(it->second.mem));
+      it = g_tw.erase(it);
+    } else {
+      ++it;
+    }
+  }
+}
+
 // the pass chain of one transform on device buffers: d_src -> d_dst through `scratch` (N elements;
 // the three buffers are distinct), enqueued on dev.stream (caller holds dev.mu)
 template <class Cfg>
@@ -763,18 +958,7 @@ static void ntt_run(Device &dev, int curve, int m, const uint64_t *gen_mont, con
   size_t need = N * elbytes + (1 << 20);
   if (host_io) need += 2 * N * elbytes;
   if (!dev.arena.try_reserve(need)) {  // out of memory: drop the other cached twiddle sets
-    {
-      std::lock_guard<std::mutex> lock(g_tw_mu);
-      ZK_CHECK(hipStreamSynchronize(dev.stream));
-      for (auto it = g_tw.begin(); it != g_tw.end();) {
-        if (std::get<0>(it->first) / 2 == dev.uid && &it->second != &tw) {
-          ZK_CHECK(hipFree(it->second.mem));
-          it = g_tw.erase(it);
-        } else {
-          ++it;
-        }
-      }
-    }
+    drop_other_twiddles(dev, tw);
     dev.arena.reserve(need);
   }
   dev.arena.reset();
@@ -815,6 +999,223 @@ static void ntt_run(Device &dev, int curve, int m, const uint64_t *gen_mont, con
   timer_collect(dev);
 }
 
+// ---------------------------------------------------------------------------- batched / coset transforms
+
+// Blocks per launch of the batched pass kernel: a batch's tiles are folded into blockIdx.x (grid
+// dimensions y and z stop at 65535), and a pass with more tiles than this runs as several launches
+// (2^21 blocks of 1024 threads stay below 2^32 work-items).  Test hook ntt_ext_set_max_grid.
+constexpr unsigned NTT_EXT_MAX_GRID = 1u << 21;
+static std::atomic<unsigned> g_ext_max_grid{0};
+void ntt_ext_set_max_grid(unsigned tiles) { g_ext_max_grid.store(tiles > NTT_EXT_MAX_GRID ? 0 : tiles); }
+
+// cached two-level power table of one coset shift: slo[i] = s^i (i < 2^h), shi[i] = s^(i 2^h)
+// (i < 2^(m-h)), s = shift (forward) or 1/shift (inverse); `scaled`: slo carries 1/N as well
+struct ShSet {
+  uint64_t *mem = nullptr;
+  uint64_t *slo = nullptr, *shi = nullptr;
+  int h = 0;
+  uint64_t last_use = 0;
+};
+// (context uid * 2 + curve, m, inverse | scaled << 1, shift)
+typedef std::tuple<int, int, int, uint64_t, uint64_t, uint64_t, uint64_t> ShKey;
+static std::map<ShKey, ShSet> g_sh;  // as g_tw: entries of a context under its mutex, the map under g_tw_mu
+static const size_t SH_CACHE_SETS = 32;  // per context (a set is 2 MiB at 2^30, 64 KiB at 2^20)
+
+template <class Cfg>
+static const ShSet &shift_table(Device &dev, int curve, int m, const uint64_t *shift_mont, bool inverse,
+                                const uint64_t *d_ninv) {
+  using F = typename Cfg::Fd;
+  using HF = typename Cfg::Fh;
+  ShKey key(dev.uid * 2 + curve, m, (inverse ? 1 : 0) | (d_ninv ? 2 : 0), shift_mont[0], shift_mont[1], shift_mont[2],
+            shift_mont[3]);
+  std::lock_guard<std::mutex> lock(g_tw_mu);
+  auto it = g_sh.find(key);
+  if (it != g_sh.end()) {
+    it->second.last_use = ++g_tw_clock;
+    return it->second;
+  }
+  const int h = m / 2;
+  const size_t el = F::N64;
+  zkh::Fe<HF> s;
+  memcpy(s.v, shift_mont, sizeof s.v);
+  if (inverse) zkh::inv(s, s);
+  std::vector<uint64_t> pows((size_t)(m > 0 ? m : 1) * HF::N, 0);
+  for (int b = 0; b < m; b++) {
+    memcpy(&pows[(size_t)b * HF::N], s.v, sizeof s.v);
+    zkh::sqr(s, s);
+  }
+  auto evict_one = [&]() -> bool {  // the context's least recently used set (its stream is idle between calls)
+    auto victim = g_sh.end();
+    size_t mine = 0;
+    for (auto i2 = g_sh.begin(); i2 != g_sh.end(); ++i2)
+      if (std::get<0>(i2->first) / 2 == dev.uid) {
+        mine++;
+        if (victim == g_sh.end() || i2->second.last_use < victim->second.last_use) victim = i2;
+      }
+    if (!mine) return false;
+    ZK_CHECK(hipStreamSynchronize(dev.stream));
+    ZK_CHECK(hipFree(victim->second.mem));
+    g_sh.erase(victim);
+    return true;
+  };
+  for (;;) {
+    size_t mine = 0;
+    for (auto &kv : g_sh) mine += std::get<0>(kv.first) / 2 == dev.uid;
+    if (mine < SH_CACHE_SETS || !evict_one()) break;
+  }
+  ShSet ss;
+  const size_t words = (((size_t)1 << h) + ((size_t)1 << (m - h))) * el + pows.size();
+  while (hipMalloc(&ss.mem, words * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    ZK_REQUIRE(evict_one(), "ntt: out of device memory for the shift table");
+  }
+  ss.slo = ss.mem;
+  ss.shi = ss.slo + ((size_t)1 << h) * el;
+  uint64_t *d_pows = ss.shi + ((size_t)1 << (m - h)) * el;
+  ss.h = h;
+  hipStream_t st = dev.stream;
+  ZK_CHECK(hipMemcpyAsync(d_pows, pows.data(), pows.size() * 8, hipMemcpyHostToDevice, st));
+  const int nt = 1 << (h > m - h ? h : m - h);
+  hipLaunchKernelGGL(k_tw_tables<F>, dim3(div_up(nt, 256)), dim3(256), 0, st, ss.slo, ss.shi, h, m, d_pows);
+  ZK_CHECK(hipGetLastError());
+  if (d_ninv) {
+    hipLaunchKernelGGL(k_sh_scale<F>, dim3(div_up((size_t)1 << h, 256)), dim3(256), 0, st, ss.slo, 1 << h, d_ninv);
+    ZK_CHECK(hipGetLastError());
+  }
+  ss.last_use = ++g_tw_clock;
+  return g_sh.emplace(key, ss).first->second;
+}
+
+// the pass chains of `batch` transforms (rows b * 2^m of d_src, d_dst and scratch), every pass one
+// launch over all of them (or several, beyond the grid cap); d_dst may be d_src
+template <class Cfg>
+static void ntt_ext_passes(Device &dev, int m, const std::vector<int> &dig, const TwSet &tw, const ShSet *sh,
+                           bool inverse, size_t batch, const uint64_t *d_src, uint64_t *d_dst, uint64_t *scratch) {
+  using F = typename Cfg::Fd;
+  const size_t N = (size_t)1 << m;
+  const int P = (int)dig.size();
+  size_t S = N, T = 1;
+  const uint64_t *in = d_src;
+  hipStream_t st = dev.stream;
+  PassArgs pa;
+  pa.m = m;
+  pa.P = P;
+  for (int p = 0; p < P && p < 8; p++) pa.dig[p] = dig[p];
+  const unsigned cap_hook = g_ext_max_grid.load();
+  const unsigned long long cap = cap_hook ? cap_hook : NTT_EXT_MAX_GRID;
+  for (int p = 0; p < P; p++) {
+    const int r = dig[p];
+    const int R = 1 << r;
+    S >>= r;
+    const int last = (p == P - 1);
+    uint64_t *out = last ? d_dst : scratch;
+    const bool big = r > 8;
+    const int tile = big ? NTT_TILE_BIG : NTT_TILE;
+    int G;  // as ntt_passes
+    if (P == 1) {
+      G = 1;
+    } else if (!last) {
+      G = tile / R;
+      if ((size_t)G > S) G = (int)S;
+    } else {
+      G = tile / R;
+      if (G > (1 << dig[0])) G = 1 << dig[0];
+    }
+    const size_t ntiles = N / ((size_t)R * G);
+    const size_t lds = (size_t)G * R * F::N * 4;
+    pa.r = r;
+    pa.S = (int)S;
+    pa.T = (int)T;
+    pa.last = last;
+    pa.G = G;
+    pa.h = tw.h;
+    pa.otf = (!last && !tw.tab[p]) ? 1 : 0;
+    ExtArgs ea;
+    ea.ntiles = (unsigned)ntiles;
+    ea.mode = !sh ? 0 : (!inverse && p == 0) ? 1 : (inverse && last) ? 2 : 0;
+    ea.sh = sh ? sh->h : 0;
+    ea.slo = sh ? sh->slo : nullptr;
+    ea.shi = sh ? sh->shi : nullptr;
+    const void *kfn =
+        big ? (const void *)k_ntt_pass_ext<F, NTT_THREADS_BIG> : (const void *)k_ntt_pass_ext<F, NTT_THREADS>;
+    ZK_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const unsigned long long total = (unsigned long long)batch * ntiles;
+    for (unsigned long long t0 = 0; t0 < total; t0 += cap) {
+      const unsigned grid = (unsigned)std::min(cap, total - t0);
+      ea.tile0 = t0;
+      if (big)
+        hipLaunchKernelGGL((k_ntt_pass_ext<F, NTT_THREADS_BIG>), dim3(grid), dim3(NTT_THREADS_BIG), lds, st, in, out,
+                           pa, tw.inner_i[p], tw.tab[p], last ? tw.scale : nullptr, tw.tlo, tw.thi, ea);
+      else
+        hipLaunchKernelGGL((k_ntt_pass_ext<F, NTT_THREADS>), dim3(grid), dim3(NTT_THREADS), lds, st, in, out, pa,
+                           tw.inner_i[p], tw.tab[p], last ? tw.scale : nullptr, tw.tlo, tw.thi, ea);
+      ZK_CHECK(hipGetLastError());
+    }
+    in = out;
+    T <<= r;
+  }
+}
+
+template <class Cfg>
+static void ntt_ext_run(Device &dev, int curve, int m, const uint64_t *gen_mont, const uint64_t *shift_mont,
+                        size_t batch, const uint64_t *src, uint64_t *dst, bool host_io, bool inverse) {
+  using F = typename Cfg::Fd;
+  const size_t N = (size_t)1 << m;
+  hipStream_t st = dev.stream;
+  std::vector<int> dig;
+  split_digits(m, dig);
+  TwSet &tw = twiddles<Cfg>(dev, curve, m, gen_mont, inverse, dig);
+  // the inverse's 1/N rides on the shift table exactly when the last pass owes it (tw.scale)
+  const ShSet *sh = shift_mont ? &shift_table<Cfg>(dev, curve, m, shift_mont, inverse, inverse ? tw.scale : nullptr)
+                               : nullptr;
+
+  // working set of c transforms at a time: scratch, and the staged source and destination of the
+  // host form; when it does not fit, the batch runs in contiguous chunks, halved down to one
+  const size_t rows = N * F::N64, rowbytes = rows * 8;
+  auto need = [&](size_t c) { return (host_io ? 3 : 1) * c * rowbytes + (1 << 20); };
+  size_t c = batch;
+  while (!dev.arena.try_reserve(need(c))) {
+    if (c > 1) {
+      c = (c + 1) / 2;
+      continue;
+    }
+    drop_other_twiddles(dev, tw);
+    dev.arena.reserve(need(1));
+    break;
+  }
+  for (size_t b0 = 0; b0 < batch; b0 += c) {
+    const size_t cb = std::min(c, batch - b0);
+    dev.arena.reset();
+    const uint64_t *d_src = src + b0 * rows;
+    uint64_t *d_dst = dst + b0 * rows;
+    if (host_io) {
+      uint64_t *a = dev.arena.take<uint64_t>(cb * rows);
+      d_dst = dev.arena.take<uint64_t>(cb * rows);
+      ZK_CHECK(hipMemcpyAsync(a, src + b0 * rows, cb * rowbytes, hipMemcpyHostToDevice, st));
+      d_src = a;
+    }
+    uint64_t *scratch = dev.arena.take<uint64_t>(cb * rows);
+    timer_begin(dev);
+    ntt_ext_passes<Cfg>(dev, m, dig, tw, sh, inverse, cb, d_src, d_dst, scratch);
+    timer_end(dev);
+    if (host_io) copy_to_host(dev, st, dst + b0 * rows, d_dst, cb * rowbytes);
+    stream_wait(dev, st);
+    timer_collect(dev);
+  }
+}
+
+int ntt_ext(int curve, int m, const uint64_t *gen_mont, const uint64_t *shift_mont, int batch, const uint64_t *src,
+            uint64_t *dst, bool host_io, bool inverse) {
+  if (m < 0 || m > 30 || batch < 0) return -1;
+  if (inverse && shift_mont && !(shift_mont[0] | shift_mont[1] | shift_mont[2] | shift_mont[3])) return -1;
+  if (batch == 0) return 0;
+  Device &dev = current_device();
+  std::lock_guard<std::mutex> lock(dev.mu);
+  if (curve == 0) ntt_ext_run<CfgBN>(dev, curve, m, gen_mont, shift_mont, (size_t)batch, src, dst, host_io, inverse);
+  else ntt_ext_run<CfgBLS>(dev, curve, m, gen_mont, shift_mont, (size_t)batch, src, dst, host_io, inverse);
+  return 0;
+}
+
 void ntt_enqueue(Device &dev, int curve, int m, const uint64_t *gen_mont, const uint64_t *d_src, uint64_t *d_dst,
                  uint64_t *scratch, bool inverse) {
   ZK_REQUIRE(m >= 0 && m <= 30, "ntt: log2 size out of range (0..30)");
@@ -830,6 +1231,14 @@ void ntt_release(Device &dev) {
     if (std::get<0>(it->first) / 2 == dev.uid) {
       ZK_CHECK(hipFree(it->second.mem));
       it = g_tw.erase(it);
+    } else {
+      ++it;
+    }
+  }
+  for (auto it = g_sh.begin(); it != g_sh.end();) {
+    if (std::get<0>(it->first) / 2 == dev.uid) {
+      ZK_CHECK(hipFree(it->second.mem));
+      it = g_sh.erase(it);
     } else {
       ++it;
     }

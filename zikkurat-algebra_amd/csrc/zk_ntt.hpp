@@ -8,6 +8,16 @@ namespace zk {
 // when host_io, device pointers otherwise.  inverse: interpolation incl. the 1/N factor.
 void ntt(int curve, int m, const uint64_t *gen_mont, const uint64_t *src, uint64_t *dst, bool host_io,
          bool inverse);
+// `batch` transforms of 2^m elements each (transform b at row offset b * 2^m), evaluated on /
+// interpolated from the coset shift * <gen> when shift_mont (HOST pointer, Montgomery Fr) is given:
+//   forward: dst_b[k] = sum_j src_b[j] shift^j gen^(j k);  inverse: dst_b[j] = shift^-j / N sum_k src_b[k] gen^(-j k)
+// On the calling thread's device; dst may equal src.  Returns 0, or -1 (nothing written) for m
+// outside 0..30, batch < 0 or an inverse with shift == 0.  When the working set of the whole batch
+// does not fit the arena the batch runs in contiguous chunks of transforms.
+int ntt_ext(int curve, int m, const uint64_t *gen_mont, const uint64_t *shift_mont, int batch, const uint64_t *src,
+            uint64_t *dst, bool host_io, bool inverse);
+// test hook: blocks per launch of the batched pass kernel (0 or above 2^21: the default, 2^21)
+void ntt_ext_set_max_grid(unsigned tiles);
 // test hook: pass split, 12 (two passes for every 2^17..2^24), 8 (<= 2^8-point passes only) or
 // 0 (default: two passes at 2^20 only)
 void ntt_set_max_radix(int r);

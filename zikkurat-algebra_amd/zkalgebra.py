@@ -77,6 +77,8 @@ REFERENCE_SYMBOLS += [f"{c}_poly_mont_{o}" for c in CURVES for o in POLY_OPS]
 EXTENSION_SYMBOLS += ["zkg_poly_mul_device", "zkg_poly_eval_device", "zkg_poly_lincomb_device",
                       "zkg_poly_set_mul_direct_max", "zkg_poly_last_mul_path"]
 POLY_MUL_MAX_LOG = {"bn128": 28, "bls12_381": 30}   # largest product, log2 of n1 + n2 - 1
+# coset and batched NTT
+EXTENSION_SYMBOLS += ["zkg_ntt_ext_device", "zkg_ntt_ext", "zkg_ntt_ext_set_max_grid"]
 
 _lib = None
 
@@ -98,6 +100,13 @@ def load():
                                           ctypes.c_void_p, U64P, ctypes.c_int]
         lib.zkg_ntt_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, U64P, ctypes.c_void_p,
                                        ctypes.c_void_p]
+        if hasattr(lib, "zkg_ntt_ext_device"):  # ZK_LIB_PATH may name an older variant build (A/B timing);
+            # calling a symbol it lacks still raises
+            lib.zkg_ntt_ext_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, U64P, U64P, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_void_p]
+            lib.zkg_ntt_ext.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, U64P, U64P, ctypes.c_int, U64P,
+                                        U64P]
+            lib.zkg_ntt_ext_set_max_grid.argtypes = [ctypes.c_uint]
         lib.zkg_g2_msm_device.argtypes = lib.zkg_g1_msm_device.argtypes
         lib.zkg_g2_batch_to_affine_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         lib.zkg_g2_fft_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, U64P, ctypes.c_void_p,
@@ -482,6 +491,58 @@ ntt = forward_ntt
 intt = inverse_ntt
 
 
+def _shift_arg(shift):
+    return None if shift is None else _p(_k(shift))
+
+
+def ntt_ext(curve, m, gen, src, inverse=False, shift=None, batch=1):
+    """zkg_ntt_ext on host arrays: `batch` transforms of 2^m rows each (src: batch * 2^m rows), on the
+    coset shift * <gen> when a shift (one Montgomery Fr) is given"""
+    src = _fr(src)
+    if batch >= 0 and 0 <= m <= 30 and src.shape[0] != batch << m:
+        raise ValueError("ntt_ext: the array does not hold batch * 2^m rows")
+    require_gpu()
+    out = np.empty_like(src)
+    rc = load().zkg_ntt_ext(CURVE_ID[curve], 1 if inverse else 0, m, _p(_k(gen)), _shift_arg(shift), batch, _p(src),
+                            _p(out))
+    if rc != 0:
+        raise ValueError("ntt_ext: log2 size outside 0..30, negative batch, or an inverse with shift 0")
+    return out
+
+
+def _ntt_batch(sg, arr, inverse, name):
+    arr = np.ascontiguousarray(arr, dtype=np.uint64)
+    if arr.ndim != 3 or arr.shape[1] != sg.size or arr.shape[2] != NLIMBS_R:
+        raise ValueError(f"{name}: expected an array of shape (B, subgroup size, 4)")
+    out = ntt_ext(sg.curve, sg.log_size, sg.gen_array(), arr.reshape(-1, NLIMBS_R), inverse=inverse,
+                  batch=arr.shape[0])
+    return out.reshape(arr.shape)
+
+
+def forward_ntt_batch(sg, polys):
+    """forwardNTT of every polynomial of a (B, 2^m, 4) array in one call (every pass one launch)"""
+    return _ntt_batch(sg, polys, False, "forwardNTT")
+
+
+def inverse_ntt_batch(sg, values):
+    """inverseNTT of every row block of a (B, 2^m, 4) array in one call"""
+    return _ntt_batch(sg, values, True, "inverseNTT")
+
+
+def coset_ntt(sg, shift, poly):
+    """evaluations f(shift * gen^k), k = 0..n-1: the shift powers ride on the first pass's load"""
+    if poly.ndim != 2 or sg.size != poly.shape[0]:
+        raise ValueError("forwardNTT: subgroup size differs from the array size")
+    return ntt_ext(sg.curve, sg.log_size, sg.gen_array(), poly, shift=shift)
+
+
+def coset_intt(sg, shift, values):
+    """interpolation from the values on the coset shift * <gen> (shift != 0)"""
+    if values.ndim != 2 or sg.size != values.shape[0]:
+        raise ValueError("inverseNTT: subgroup size differs from the array size")
+    return ntt_ext(sg.curve, sg.log_size, sg.gen_array(), values, inverse=True, shift=shift)
+
+
 # ----------------------------------------------------------------------------- Fr vectors
 
 def _fr(a):
@@ -860,6 +921,20 @@ def poly_last_mul_path():
 def ntt_device(curve, m, gen, d_src, d_dst, inverse=False):
     load().zkg_ntt_device(CURVE_ID[curve], 1 if inverse else 0, m, _p(np.ascontiguousarray(gen)), d_src.ptr,
                           d_dst.ptr)
+
+
+def ntt_ext_device(curve, m, gen, d_src, d_dst, inverse=False, shift=None, batch=1):
+    """device-resident batched / coset NTT (zkg_ntt_ext_device): d_src / d_dst are DeviceBuffers of
+    batch * 2^m rows (the same buffer transforms in place); raises ValueError on a -1 return"""
+    rc = load().zkg_ntt_ext_device(CURVE_ID[curve], 1 if inverse else 0, m, _p(_k(gen)), _shift_arg(shift), batch,
+                                   d_src.ptr if d_src else None, d_dst.ptr if d_dst else None)
+    if rc != 0:
+        raise ValueError("ntt_ext_device: log2 size outside 0..30, negative batch, or an inverse with shift 0")
+
+
+def ntt_ext_set_max_grid(tiles):
+    """test hook: blocks per launch of the batched NTT pass kernel (0: the default, 2^21)"""
+    load().zkg_ntt_ext_set_max_grid(int(tiles))
 
 
 def ntt_set_table_max(entries):
