@@ -75,10 +75,16 @@ def test_model_constants_are_the_kernels():
     assert subs == [tuple(str(v) for v in lb.NTT_DFT_SUB)]  # every other difference is the default <4, 1>
     hdr = open(os.path.join(ROOT, "zikkurat-algebra_amd", "csrc", "zk_field.hpp")).read()
     assert re.search(r"template <class F, int K = 4, int BW = 1>\s*__device__ __forceinline__ void fe_sub_lazy", hdr)
-    # the ext kernel canonicalises the shifted input and closes the inverse shift through fe_store_ref
-    ext = src[src.index("void __launch_bounds__(NT) k_ntt_pass_ext"):src.index("k_sh_scale")]
+    # the pass body (shared by both kernels) canonicalises the shifted input and closes the inverse
+    # shift through fe_store_ref
+    ext = src[src.index("void ntt_pass_body("):src.index("k_sh_scale")]
     assert re.search(r"fe_mul\(y, x, w\);\s*fe_canon\(y\);", ext)
     assert re.search(r"tw2\(w, ext\.slo, ext\.shi, ext\.sh, \(uint32_t\)addr\);\s*fe_mul\(y, x, w\);\s*fe_store_ref", ext)
+    # one body: one DFT call and one product-free closing loop in the file, behind both kernel names
+    assert src.count("lds_dft<F, NT>(") == 1
+    assert src.count("fe_reduce_small(x);") == 1
+    for kernel in ("k_ntt_pass", "k_ntt_pass_ext"):
+        assert re.search(r"__global__ void __launch_bounds__\(NT\)\s+" + kernel + r"\(", src), kernel
 
 
 @pytest.mark.parametrize("field", FR_FIELDS)

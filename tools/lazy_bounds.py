@@ -538,7 +538,7 @@ def ntt_fixed_point(F):
 
 
 def ntt_ext_paths(F):
-    """zk_ntt.hip k_ntt_pass_ext, the coset shift fused into the batched pass kernel.
+    """zk_ntt.hip ntt_pass_body<EXT = true> (k_ntt_pass_ext), the coset shift fused into the batched pass kernel.
     Forward: pass 0 multiplies the loaded word (any 256-bit pattern, canonical in a valid input) by
     tw2 of the shift table (a product of two canonical entries) before lds_put.  The product is only
     known to be < 2p, and lds_dft does NOT take < 2p inputs: the first radix-4 round's

@@ -17,6 +17,11 @@ half-rate slot, other 32-bit VALU half a slot) times those trip counts, summed o
 of every pass of a transform (zk_ntt.hip split_digits), give the issue slots per transform;
 bench.py divides them by the measured pass-chain time and the measured issue ceiling
 (profiles/*valu_ceiling*.json).
+
+The data loops are named by their order in the assembly (LOOP_ORDER), so a build that lays the four
+closing loops out in another order is mislabelled without an error: compare the per-loop slots with
+the previous build's after any change to the pass body (zk_ntt.hip ntt_pass_body takes its argument
+structs by value because taking them by reference reordered those loops).
 """
 import json
 import os

@@ -293,137 +293,10 @@ static size_t ntt_table_max() {
   return v ? v : ZK_NTT_TABLE_MAX;
 }
 
-// One pass.  Block = one tile of G instances x R elements.
-//   non-last pass: instance (hi, lo), lo in [0, S); element k at hi*R*S + k*S + lo
-//                  tile = G consecutive lo for one hi; output * tab[k*S + lo]
-//   last pass    : S == 1; instance = position prefix (k_0..k_{P-2}); element k at inst*R + k;
-//                  tile = G instances with consecutive k_0; output to natural index
-template <class F, int NT>
-__global__ void __launch_bounds__(NT) k_ntt_pass(const uint64_t *__restrict__ src, uint64_t *__restrict__ dst,
-                                                          PassArgs a, const uint32_t *__restrict__ itw_i,
-                                                          const uint64_t *__restrict__ tab,
-                                                          const uint64_t *__restrict__ scale,
-                                                          const uint64_t *__restrict__ tlo,
-                                                          const uint64_t *__restrict__ thi) {
-  extern __shared__ uint32_t lds[];
-  constexpr int NW = F::N;
-  const int r = a.r, G = a.G, S = a.S;
-  const int R = 1 << r;
-  uint32_t *data = lds;                          // [G][R] elements
-  const uint32_t *itw = (const uint32_t *)__builtin_assume_aligned(itw_i, 16);  // [R/2] inner twiddles
-  const int tid = threadIdx.x;
-  const int tile = blockIdx.x;
-
-  // instance geometry of this tile
-  size_t hi_base = 0;  // non-last: hi * R * S + lo0
-  size_t pos_base = 0, nat_base = 0;  // last: position / natural index of instance k_0 = k0base
-  int k0base = 0, k0stride_pos = 0;
-  if (!a.last) {
-    const int ntl = S / G;
-    hi_base = (size_t)(tile / ntl) * R * S + (size_t)(tile % ntl) * G;
-  } else if (a.P > 1) {
-    const int R0 = 1 << a.dig[0];
-    const int ntile0 = R0 / G;
-    k0base = (tile % ntile0) * G;
-    int rem = tile / ntile0;
-    size_t Sq = (size_t)1 << a.m;
-    size_t Tq = (size_t)R0;
-    for (int q = 0; q < a.P - 1; q++) {
-      Sq >>= a.dig[q];
-      if (q == 0) {
-        k0stride_pos = (int)(Sq >> r);  // position stride of k_0, in units of R
-      } else {
-        const int kq = rem & ((1 << a.dig[q]) - 1);
-        rem >>= a.dig[q];
-        pos_base += (size_t)kq * Sq;
-        nat_base += (size_t)kq * Tq;
-        Tq <<= a.dig[q];
-      }
-    }
-  }
-
-  // load: element (g, k) -> LDS slot g*R + bitrev_r(k)
-  const int nel = G * R;
-  for (int e = tid; e < nel; e += NT) {
-    int g, k;
-    size_t addr;
-    if (!a.last) {
-      g = e % G;
-      k = e / G;
-      addr = hi_base + (size_t)k * S + g;
-    } else {
-      g = e / R;
-      k = e % R;
-      addr = pos_base + ((size_t)(k0base + g) * k0stride_pos) * R + k;
-      if (a.P == 1) addr = k;
-    }
-    Fe<F> x;
-    fe_load_ref(x, src + addr * F::N64);
-    const int kr = r ? (int)(__builtin_bitreverse32((uint32_t)k) >> (32 - r)) : 0;
-    lds_put(data + (size_t)lds_slot((uint32_t)(g * R + kr)) * NW, x);
-  }
-  __syncthreads();
-
-  lds_dft<F, NT>(data, itw, r, G);
-
-  // Output: one loop per closing mode (uniform per launch), so every mode is its own loop in
-  // the ISA (tools/ntt_isa_model.py prices each pass from these loops)
-  //   non-last pass: x * w, w from the pass's table or (otf) tw2; stored packed, not canonical
-  //                  (a product is < 2p < 2^256; the next pass only multiplies and adds it)
-  //   last pass:     the lazily grown value (< 50p) back below 2p, as fe_store_ref's
-  //                  canonicalisation needs -- by the product with the scale (1/N) when an
-  //                  inverse's scale has no table to ride on, else by a product-free reduction
-  auto out_addr = [&](int g, int k) -> size_t {
-    if (!a.last) return hi_base + (size_t)k * S + g;
-    return (a.P == 1) ? (size_t)k : nat_base + (size_t)(k0base + g) + (size_t)k * a.T;
-  };
-  if (!a.last && !a.otf) {
-    for (int e = tid; e < nel; e += NT) {
-      const int g = e % G, k = e / G;  // consecutive threads -> consecutive g (coalesced)
-      Fe<F> x, w, y;
-      lds_get(x, data + (size_t)lds_slot((uint32_t)(g * R + k)) * NW);
-      const size_t addr = out_addr(g, k);
-      fe_load_ref(w, tab + ((size_t)k * S + (addr % S)) * F::N64);
-      fe_mul(y, x, w);
-      fe_store_packed(dst + addr * F::N64, y);
-    }
-  } else if (!a.last) {
-    for (int e = tid; e < nel; e += NT) {
-      const int g = e % G, k = e / G;
-      Fe<F> x, w, y;
-      lds_get(x, data + (size_t)lds_slot((uint32_t)(g * R + k)) * NW);
-      const size_t addr = out_addr(g, k);
-      tw2(w, tlo, thi, a.h, (uint32_t)a.T * (uint32_t)k * (uint32_t)(addr % S));
-      fe_mul(y, x, w);
-      fe_store_packed(dst + addr * F::N64, y);
-    }
-  } else if (scale) {
-    Fe<F> sc, t;
-    fe_load_ref(t, scale);
-    fe_to_int(sc, t);
-    for (int e = tid; e < nel; e += NT) {
-      const int g = e % G, k = e / G;
-      Fe<F> x, y;
-      lds_get(x, data + (size_t)lds_slot((uint32_t)(g * R + k)) * NW);
-      fe_mul(y, x, sc);
-      fe_store_ref(dst + out_addr(g, k) * F::N64, y);
-    }
-  } else {
-    for (int e = tid; e < nel; e += NT) {
-      const int g = e % G, k = e / G;
-      Fe<F> x;
-      lds_get(x, data + (size_t)lds_slot((uint32_t)(g * R + k)) * NW);
-      fe_reduce_small(x);
-      fe_store_ref(dst + out_addr(g, k) * F::N64, x);
-    }
-  }
-}
-
-// What the extended pass kernel (k_ntt_pass_ext) adds to a pass: the batch geometry of the launch
-// and the coset shift.  Block blockIdx.x of the launch is tile (tile0 + blockIdx.x) % ntiles of
-// transform (tile0 + blockIdx.x) / ntiles; transform b lives at row offset b * 2^m of src, dst.
-// slo / shi: two-level power table of the shift (forward) or of its inverse (inverse), laid out as
-// tlo / thi with split sh.
+// What the batched pass kernel (k_ntt_pass_ext) adds to a pass: the batch geometry of the launch and the coset shift.
+// Block blockIdx.x of the launch is tile (tile0 + blockIdx.x) % ntiles of transform (tile0 + blockIdx.x) / ntiles;
+// transform b lives at row offset b * 2^m of src, dst.  slo / shi: two-level power table of the shift (forward) or
+// of its inverse (inverse), laid out as tlo / thi with split sh.
 struct ExtArgs {
   unsigned long long tile0;  // global tile index of block 0 of this launch
   unsigned ntiles;           // tiles per transform in this pass
@@ -432,29 +305,32 @@ struct ExtArgs {
   const uint64_t *slo, *shi;
 };
 
-// One pass of a whole batch of transforms, with the coset shift fused in (zkg_ntt_ext*): k_ntt_pass's
-// tile geometry, lds_dft and closing modes, and beside them the batch index (the tile and the
-// transform come from ExtArgs), the shift product on the load of pass 0 and the inverse shift as
-// one more closing mode of the last pass.  A kernel of its own, so that k_ntt_pass -- what every
-// single-transform entry point launches -- keeps its source and its registers.
-template <class F, int NT>
-__global__ void __launch_bounds__(NT) k_ntt_pass_ext(const uint64_t *__restrict__ src_all,
-                                                              uint64_t *__restrict__ dst_all, PassArgs a,
-                                                              const uint32_t *__restrict__ itw_i,
-                                                              const uint64_t *__restrict__ tab,
-                                                              const uint64_t *__restrict__ scale,
-                                                              const uint64_t *__restrict__ tlo,
-                                                              const uint64_t *__restrict__ thi, ExtArgs ext) {
+// One pass, the body of both pass kernels.  Block = one tile of G instances x R elements.
+//   non-last pass: instance (hi, lo), lo in [0, S); element k at hi*R*S + k*S + lo
+//                  tile = G consecutive lo for one hi; output * tab[k*S + lo]
+//   last pass    : S == 1; instance = position prefix (k_0..k_{P-2}); element k at inst*R + k;
+//                  tile = G instances with consecutive k_0; output to natural index
+// EXT (k_ntt_pass_ext) adds what ExtArgs describes: the tile and the transform of a block, the shift product on the
+// load of pass 0 and the inverse shift as one more closing mode; without it `ext` is never read.
+template <class F, int NT, bool EXT>
+__device__ __forceinline__ void ntt_pass_body(const uint64_t *__restrict__ src_all, uint64_t *__restrict__ dst_all,
+                                              PassArgs a, const uint32_t *__restrict__ itw_i,
+                                              const uint64_t *__restrict__ tab, const uint64_t *__restrict__ scale,
+                                              const uint64_t *__restrict__ tlo, const uint64_t *__restrict__ thi,
+                                              ExtArgs ext) {
   extern __shared__ uint32_t lds[];
   constexpr int NW = F::N;
-  const int r = a.r, G = a.G, S = a.S;
-  const int R = 1 << r;
+  const int r = a.r, G = a.G, S = a.S, R = 1 << r;
   uint32_t *data = lds;                          // [G][R] elements
   const uint32_t *itw = (const uint32_t *)__builtin_assume_aligned(itw_i, 16);  // [R/2] inner twiddles
   const int tid = threadIdx.x;
-  const unsigned long long gt = ext.tile0 + blockIdx.x;
-  const int tile = (int)(gt % ext.ntiles);
-  const size_t row0 = (size_t)(gt / ext.ntiles) << a.m;  // this transform's rows
+  int tile = blockIdx.x;
+  size_t row0 = 0;  // this transform's rows
+  if constexpr (EXT) {
+    const unsigned long long gt = ext.tile0 + blockIdx.x;
+    tile = (int)(gt % ext.ntiles);
+    row0 = (size_t)(gt / ext.ntiles) << a.m;
+  }
   const uint64_t *__restrict__ src = src_all + row0 * F::N64;
   uint64_t *__restrict__ dst = dst_all + row0 * F::N64;
 
@@ -466,12 +342,10 @@ __global__ void __launch_bounds__(NT) k_ntt_pass_ext(const uint64_t *__restrict_
     const int ntl = S / G;
     hi_base = (size_t)(tile / ntl) * R * S + (size_t)(tile % ntl) * G;
   } else if (a.P > 1) {
-    const int R0 = 1 << a.dig[0];
-    const int ntile0 = R0 / G;
+    const int R0 = 1 << a.dig[0], ntile0 = R0 / G;
     k0base = (tile % ntile0) * G;
     int rem = tile / ntile0;
-    size_t Sq = (size_t)1 << a.m;
-    size_t Tq = (size_t)R0;
+    size_t Sq = (size_t)1 << a.m, Tq = (size_t)R0;
     for (int q = 0; q < a.P - 1; q++) {
       Sq >>= a.dig[q];
       if (q == 0) {
@@ -503,7 +377,7 @@ __global__ void __launch_bounds__(NT) k_ntt_pass_ext(const uint64_t *__restrict_
     }
     Fe<F> x;
     fe_load_ref(x, src + addr * F::N64);
-    if (ext.mode == 1) {
+    if (EXT && ext.mode == 1) {
       // pass 0 reads natural order: addr is the input index j.  x * shift^j is only < 2p, which
       // lds_dft's first radix-4 round does not take (its a2 = b0 + 4p - s23 needs s23's top limb
       // within 4p's borrowed one: tools/lazy_bounds.py ntt_ext_paths), so it is canonicalised and
@@ -521,70 +395,74 @@ __global__ void __launch_bounds__(NT) k_ntt_pass_ext(const uint64_t *__restrict_
 
   lds_dft<F, NT>(data, itw, r, G);
 
-  // Output: one loop per closing mode (uniform per launch), so every mode is its own loop in
-  // the ISA (tools/ntt_isa_model.py prices each pass from these loops)
+  // Output, one loop per closing mode (uniform per launch): tools/ntt_isa_model.py prices each pass from these loops
   //   non-last pass: x * w, w from the pass's table or (otf) tw2; stored packed, not canonical
   //                  (a product is < 2p < 2^256; the next pass only multiplies and adds it)
-  //   last pass:     the lazily grown value (< 50p) back below 2p, as fe_store_ref's
-  //                  canonicalisation needs -- by the product with the scale (1/N) when an
-  //                  inverse's scale has no table to ride on, else by a product-free reduction
-  auto out_addr = [&](int g, int k) -> size_t {
-    if (!a.last) return hi_base + (size_t)k * S + g;
-    return (a.P == 1) ? (size_t)k : nat_base + (size_t)(k0base + g) + (size_t)k * a.T;
-  };
-  if (!a.last && !a.otf) {
+  //   last pass:     the lazily grown value (< 50p) below 2p, as fe_store_ref's canonicalisation needs -- by the
+  //                  product with the scale (1/N) when an inverse's scale has no table, else by a product-free reduction
+  auto close = [&](auto fn) {  // fn(x, k, addr) closes element k of an instance and stores it at addr
     for (int e = tid; e < nel; e += NT) {
       const int g = e % G, k = e / G;  // consecutive threads -> consecutive g (coalesced)
-      Fe<F> x, w, y;
+      Fe<F> x;
       lds_get(x, data + (size_t)lds_slot((uint32_t)(g * R + k)) * NW);
-      const size_t addr = out_addr(g, k);
+      fn(x, k, !a.last ? hi_base + (size_t)k * S + g : a.P == 1 ? k : nat_base + (k0base + g) + (size_t)k * a.T);
+    }
+  };
+  if (!a.last && !a.otf) {
+    close([&](Fe<F> &x, int k, size_t addr) {
+      Fe<F> w, y;
       fe_load_ref(w, tab + ((size_t)k * S + (addr % S)) * F::N64);
       fe_mul(y, x, w);
       fe_store_packed(dst + addr * F::N64, y);
-    }
+    });
   } else if (!a.last) {
-    for (int e = tid; e < nel; e += NT) {
-      const int g = e % G, k = e / G;
-      Fe<F> x, w, y;
-      lds_get(x, data + (size_t)lds_slot((uint32_t)(g * R + k)) * NW);
-      const size_t addr = out_addr(g, k);
+    close([&](Fe<F> &x, int k, size_t addr) {
+      Fe<F> w, y;
       tw2(w, tlo, thi, a.h, (uint32_t)a.T * (uint32_t)k * (uint32_t)(addr % S));
       fe_mul(y, x, w);
       fe_store_packed(dst + addr * F::N64, y);
-    }
-  } else if (ext.mode == 2) {
-    // inverse coset: output j times shift^-j, the table's low half carrying 1/N when this pass owes
-    // it (the host passes no `scale` then); the lazily grown value (< 50p) times tw2's product
-    // (< 1.02p) is < 2p, as fe_store_ref needs
-    for (int e = tid; e < nel; e += NT) {
-      const int g = e % G, k = e / G;
-      Fe<F> x, w, y;
-      lds_get(x, data + (size_t)lds_slot((uint32_t)(g * R + k)) * NW);
-      const size_t addr = out_addr(g, k);
+    });
+  } else if (EXT && ext.mode == 2) {
+    // inverse coset: output j times shift^-j, the table's low half carrying 1/N when this pass owes it (the host passes
+    // no `scale` then); the lazily grown value (< 50p) times tw2's product (< 1.02p) is < 2p, as fe_store_ref needs
+    close([&](Fe<F> &x, int, size_t addr) {
+      Fe<F> w, y;
       tw2(w, ext.slo, ext.shi, ext.sh, (uint32_t)addr);
       fe_mul(y, x, w);
       fe_store_ref(dst + addr * F::N64, y);
-    }
+    });
   } else if (scale) {
     Fe<F> sc, t;
     fe_load_ref(t, scale);
     fe_to_int(sc, t);
-    for (int e = tid; e < nel; e += NT) {
-      const int g = e % G, k = e / G;
-      Fe<F> x, y;
-      lds_get(x, data + (size_t)lds_slot((uint32_t)(g * R + k)) * NW);
+    close([&](Fe<F> &x, int, size_t addr) {
+      Fe<F> y;
       fe_mul(y, x, sc);
-      fe_store_ref(dst + out_addr(g, k) * F::N64, y);
-    }
+      fe_store_ref(dst + addr * F::N64, y);
+    });
   } else {
-    for (int e = tid; e < nel; e += NT) {
-      const int g = e % G, k = e / G;
-      Fe<F> x;
-      lds_get(x, data + (size_t)lds_slot((uint32_t)(g * R + k)) * NW);
+    close([&](Fe<F> &x, int, size_t addr) {
       fe_reduce_small(x);
-      fe_store_ref(dst + out_addr(g, k) * F::N64, x);
-    }
+      fe_store_ref(dst + addr * F::N64, x);
+    });
   }
+}
+
+// The two kernels around that body; the plain one takes no ExtArgs (nine SGPRs) and divides no 64-bit tile index.
+template <class F, int NT>
+__global__ void __launch_bounds__(NT)
+    k_ntt_pass(const uint64_t *__restrict__ src, uint64_t *__restrict__ dst, PassArgs a,
+               const uint32_t *__restrict__ itw_i, const uint64_t *__restrict__ tab, const uint64_t *__restrict__ scale,
+               const uint64_t *__restrict__ tlo, const uint64_t *__restrict__ thi) {
+  ntt_pass_body<F, NT, false>(src, dst, a, itw_i, tab, scale, tlo, thi, ExtArgs{});
+}
+template <class F, int NT>
+__global__ void __launch_bounds__(NT)
+    k_ntt_pass_ext(const uint64_t *__restrict__ src_all, uint64_t *__restrict__ dst_all, PassArgs a,
+                   const uint32_t *__restrict__ itw_i, const uint64_t *__restrict__ tab,
+                   const uint64_t *__restrict__ scale, const uint64_t *__restrict__ tlo,
+                   const uint64_t *__restrict__ thi, ExtArgs ext) {
+  ntt_pass_body<F, NT, true>(src_all, dst_all, a, itw_i, tab, scale, tlo, thi, ext);
 }
 
 // shift table: slo[i] *= scale (1/N, reference form), i < n
@@ -628,6 +506,12 @@ static void split_digits(int m, std::vector<int> &d) {
   for (int p = 0; p < P; p++) d.push_back(base + (p < extra ? 1 : 0));
 }
 
+// a curve's device and host scalar field, and the one curve dispatch: fn(CfgBN{}) for curve 0, fn(CfgBLS{}) otherwise
+struct CfgBN { using Fd = BN_Fr; using Fh = zkh::BN_Fr; static constexpr int curve = 0; };
+struct CfgBLS { using Fd = BLS_Fr; using Fh = zkh::BLS_Fr; static constexpr int curve = 1; };
+template <class Fn>
+static void with_cfg(int curve, Fn fn) { curve == 0 ? fn(CfgBN{}) : fn(CfgBLS{}); }
+
 // cached twiddle set for one (curve, m, gen, direction)
 struct TwSet {
   uint64_t *mem = nullptr;       // one allocation
@@ -647,14 +531,45 @@ static std::mutex g_tw_mu;          // guards the map structure itself
 static uint64_t g_tw_clock = 0;
 static const size_t TW_CACHE_LIMIT = (size_t)8 << 30;
 
+// The per-context walk of a cache map (g_tw, g_sh: the first key field is context uid * 2 + curve), under g_tw_mu:
+// fn(it) for every entry of the context; fn may erase it
+template <class M, class Fn>
+static void for_context(M &map, const Device &dev, Fn fn) {
+  for (auto it = map.begin(); it != map.end();) {
+    const auto cur = it++;
+    if (std::get<0>(cur->first) / 2 == dev.uid) fn(cur);
+  }
+}
+// frees the context's entries but `keep` (the caller has drained the stream, or the context is closing)
+template <class M>
+static void drop_entries(M &map, const Device &dev, const void *keep = nullptr) {
+  for_context(map, dev, [&](auto it) {
+    if (&it->second == keep) return;
+    ZK_CHECK(hipFree(it->second.mem));
+    map.erase(it);
+  });
+}
+// frees the context's least recently used entry, once its stream has drained (false: it has none)
+template <class M>
+static bool evict_lru(M &map, Device &dev) {
+  auto victim = map.end();
+  for_context(map, dev, [&](auto it) {
+    if (victim == map.end() || it->second.last_use < victim->second.last_use) victim = it;
+  });
+  if (victim == map.end()) return false;
+  ZK_CHECK(hipStreamSynchronize(dev.stream));
+  ZK_CHECK(hipFree(victim->second.mem));
+  map.erase(victim);
+  return true;
+}
+
 template <class Cfg>
-static TwSet &twiddles(Device &dev, int curve, int m, const uint64_t *gen_mont, bool inverse,
-                       const std::vector<int> &dig) {
+static TwSet &twiddles(Device &dev, int m, const uint64_t *gen_mont, bool inverse, const std::vector<int> &dig) {
   using F = typename Cfg::Fd;
   using HF = typename Cfg::Fh;
   // the tables depend on the pass split too (the test hook can change it between calls)
   const size_t table_max = ntt_table_max();
-  TwKey key(dev.uid * 2 + curve, m | (dig[0] << 8), inverse, gen_mont[0], gen_mont[1], gen_mont[2], gen_mont[3],
+  TwKey key(dev.uid * 2 + Cfg::curve, m | (dig[0] << 8), inverse, gen_mont[0], gen_mont[1], gen_mont[2], gen_mont[3],
             table_max);
   std::lock_guard<std::mutex> lock(g_tw_mu);
   auto it = g_tw.find(key);
@@ -702,29 +617,16 @@ static TwSet &twiddles(Device &dev, int curve, int m, const uint64_t *gen_mont, 
   }
   // evict least-recently used sets of this context beyond the cache limit (and, when the
   // device is out of memory, until the new set fits)
-  auto evict_one = [&]() -> bool {
-    auto victim = g_tw.end();
-    for (auto i2 = g_tw.begin(); i2 != g_tw.end(); ++i2)
-      if (std::get<0>(i2->first) / 2 == dev.uid &&
-          (victim == g_tw.end() || i2->second.last_use < victim->second.last_use))
-        victim = i2;
-    if (victim == g_tw.end()) return false;
-    ZK_CHECK(hipStreamSynchronize(dev.stream));
-    ZK_CHECK(hipFree(victim->second.mem));
-    g_tw.erase(victim);
-    return true;
-  };
   for (;;) {
     size_t total = words * 8;
-    for (auto &kv : g_tw)
-      if (std::get<0>(kv.first) / 2 == dev.uid) total += kv.second.bytes;
-    if (total <= TW_CACHE_LIMIT || !evict_one()) break;
+    for_context(g_tw, dev, [&](auto it2) { total += it2->second.bytes; });
+    if (total <= TW_CACHE_LIMIT || !evict_lru(g_tw, dev)) break;
   }
   TwSet ts;
   ts.bytes = words * 8;
   while (hipMalloc(&ts.mem, ts.bytes) != hipSuccess) {
     (void)hipGetLastError();
-    ZK_REQUIRE(evict_one(), "ntt: out of device memory for the twiddle tables");
+    ZK_REQUIRE(evict_lru(g_tw, dev), "ntt: out of device memory for the twiddle tables");
   }
   uint64_t *cur = ts.mem;
   auto take = [&](size_t w) { uint64_t *p = cur; cur += (w + 1) & ~size_t(1); return p; };
@@ -781,8 +683,6 @@ static TwSet &twiddles(Device &dev, int curve, int m, const uint64_t *gen_mont, 
   return g_tw.emplace(key, ts).first->second;
 }
 
-struct CfgBN { using Fd = BN_Fr; using Fh = zkh::BN_Fr; };
-struct CfgBLS { using Fd = BLS_Fr; using Fh = zkh::BLS_Fr; };
 
 // Host I/O spread over a device set (zkg_set_devices): the transform runs on the first listed
 // device; chunk k of the input / output crosses PCIe through listed device k (its own link) and
@@ -876,83 +776,66 @@ static void spread_out(Device &dev0, const Spread &sp, uint64_t *h, const uint64
 static void drop_other_twiddles(Device &dev, const TwSet &keep) {
   std::lock_guard<std::mutex> lock(g_tw_mu);
   ZK_CHECK(hipStreamSynchronize(dev.stream));
-  for (auto it = g_tw.begin(); it != g_tw.end();) {
-    if (std::get<0>(it->first) / 2 == dev.uid && &it->second != &keep) {
-      ZK_CHECK(hipFree(it->second.mem));
-      it = g_tw.erase(it);
-    } else {
-      ++it;
-    }
-  }
+  drop_entries(g_tw, dev, &keep);
 }
 
-// the pass chain of one transform on device buffers: d_src -> d_dst through `scratch` (N elements;
+// Pass p of a 2^m transform split into `dig`: the kernel's arguments, with the tile's G rule.
+static PassArgs plan_pass(int m, const std::vector<int> &dig, int p, const TwSet &tw) {
+  const int P = (int)dig.size(), r = dig[p], last = (p == P - 1);
+  int below = 0;  // log2 T_p
+  for (int q = 0; q < p; q++) below += dig[q];
+  const int S = 1 << (m - below - r);
+  int G = (r > 8 ? NTT_TILE_BIG : NTT_TILE) >> r;  // columns (non-last) or k_0 instances (last) of a tile
+  if (P == 1) G = 1;
+  else if (!last) G = std::min(G, S);
+  else G = std::min(G, 1 << dig[0]);
+  PassArgs a = {m, r, S, 1 << below, last, G, P, tw.h, !last && !tw.tab[p], {}};  // m r S T last G P h otf dig
+  std::copy_n(dig.begin(), std::min(P, 8), a.dig);
+  return a;
+}
+static size_t pass_tiles(const PassArgs &a) { return ((size_t)1 << (a.m - a.r)) / a.G; }  // workgroups per transform
+
+// One launch of pass `a` (pass p of `tw`) by k_ntt_pass_ext (EXT, with its ExtArgs) or k_ntt_pass: the 256- /
+// 1024-thread choice, the LDS attribute, the timer's begin event when it opens a timed chain, and the launch check.
+template <class F, bool EXT, class... Ext>
+static void launch_pass(Device &dev, bool begin_timer, const PassArgs &a, unsigned grid, const uint64_t *in,
+                        uint64_t *out, const TwSet &tw, int p, const Ext &...ext) {
+  const bool big = a.r > 8;  // 2^9..2^12-point DFTs: 1024 threads over 4096-element tiles
+  const size_t lds = ((size_t)a.G << a.r) * F::N * 4;  // one tile
+  const auto kfn = [&] {
+    if constexpr (EXT) return big ? &k_ntt_pass_ext<F, NTT_THREADS_BIG> : &k_ntt_pass_ext<F, NTT_THREADS>;
+    else return big ? &k_ntt_pass<F, NTT_THREADS_BIG> : &k_ntt_pass<F, NTT_THREADS>;
+  }();
+  ZK_CHECK(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (begin_timer) timer_begin(dev);
+  hipLaunchKernelGGL(kfn, dim3(grid), dim3(big ? NTT_THREADS_BIG : NTT_THREADS), lds, dev.stream, in, out, a,
+                     tw.inner_i[p], tw.tab[p], a.last ? tw.scale : nullptr, tw.tlo, tw.thi, ext...);
+  ZK_CHECK(hipGetLastError());
+}
+
+// the pass chain of one transform on device buffers: in -> d_dst through `scratch` (N elements;
 // the three buffers are distinct), enqueued on dev.stream (caller holds dev.mu)
 template <class Cfg>
-static void ntt_passes(Device &dev, int m, const std::vector<int> &dig, const TwSet &tw, const uint64_t *d_src,
+static void ntt_passes(Device &dev, int m, const std::vector<int> &dig, const TwSet &tw, const uint64_t *in,
                        uint64_t *d_dst, uint64_t *scratch, bool timed) {
-  using F = typename Cfg::Fd;
-  const size_t N = (size_t)1 << m;
-  const int P = (int)dig.size();
-  size_t S = N, T = 1;
-  const uint64_t *in = d_src;
-  hipStream_t st = dev.stream;
-  PassArgs pa;
-  pa.m = m;
-  pa.P = P;
-  for (int p = 0; p < P && p < 8; p++) pa.dig[p] = dig[p];
-  for (int p = 0; p < P; p++) {
-    const int r = dig[p];
-    const int R = 1 << r;
-    S >>= r;
-    const int last = (p == P - 1);
-    uint64_t *out = last ? d_dst : scratch;
-    const bool big = r > 8;  // 2^9..2^12-point DFTs: 1024 threads over 4096-element tiles
-    const int tile = big ? NTT_TILE_BIG : NTT_TILE;
-    int G;
-    if (P == 1) {
-      G = 1;
-    } else if (!last) {
-      G = tile / R;
-      if ((size_t)G > S) G = (int)S;
-    } else {
-      G = tile / R;
-      if (G > (1 << dig[0])) G = 1 << dig[0];
-    }
-    const size_t ntiles = N / ((size_t)R * G);
-    const size_t lds = (size_t)G * R * F::N * 4;
-    pa.r = r;
-    pa.S = (int)S;
-    pa.T = (int)T;
-    pa.last = last;
-    pa.G = G;
-    pa.h = tw.h;
-    pa.otf = (!last && !tw.tab[p]) ? 1 : 0;
-    const void *kfn = big ? (const void *)k_ntt_pass<F, NTT_THREADS_BIG> : (const void *)k_ntt_pass<F, NTT_THREADS>;
-    ZK_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (p == 0 && timed) timer_begin(dev);
-    if (big)
-      hipLaunchKernelGGL((k_ntt_pass<F, NTT_THREADS_BIG>), dim3((unsigned)ntiles), dim3(NTT_THREADS_BIG), lds, st, in,
-                         out, pa, tw.inner_i[p], tw.tab[p], last ? tw.scale : nullptr, tw.tlo, tw.thi);
-    else
-      hipLaunchKernelGGL((k_ntt_pass<F, NTT_THREADS>), dim3((unsigned)ntiles), dim3(NTT_THREADS), lds, st, in, out,
-                         pa, tw.inner_i[p], tw.tab[p], last ? tw.scale : nullptr, tw.tlo, tw.thi);
-    ZK_CHECK(hipGetLastError());
-    if (last && timed) timer_end(dev);
+  for (int p = 0; p < (int)dig.size(); p++) {
+    const PassArgs a = plan_pass(m, dig, p, tw);
+    uint64_t *out = a.last ? d_dst : scratch;
+    launch_pass<typename Cfg::Fd, false>(dev, p == 0 && timed, a, (unsigned)pass_tiles(a), in, out, tw, p);
+    if (a.last && timed) timer_end(dev);
     in = out;
-    T <<= r;
   }
 }
 
 template <class Cfg>
-static void ntt_run(Device &dev, int curve, int m, const uint64_t *gen_mont, const uint64_t *src, uint64_t *dst,
+static void ntt_run(Device &dev, int m, const uint64_t *gen_mont, const uint64_t *src, uint64_t *dst,
                     bool host_io, bool inverse, const Spread *sp = nullptr) {
   using F = typename Cfg::Fd;
   const size_t N = (size_t)1 << m;
   hipStream_t st = dev.stream;
   std::vector<int> dig;
   split_digits(m, dig);
-  TwSet &tw = twiddles<Cfg>(dev, curve, m, gen_mont, inverse, dig);
+  TwSet &tw = twiddles<Cfg>(dev, m, gen_mont, inverse, dig);
 
   const size_t elbytes = (size_t)F::N64 * 8;
   size_t need = N * elbytes + (1 << 20);
@@ -1022,12 +905,11 @@ static std::map<ShKey, ShSet> g_sh;  // as g_tw: entries of a context under its 
 static const size_t SH_CACHE_SETS = 32;  // per context (a set is 2 MiB at 2^30, 64 KiB at 2^20)
 
 template <class Cfg>
-static const ShSet &shift_table(Device &dev, int curve, int m, const uint64_t *shift_mont, bool inverse,
-                                const uint64_t *d_ninv) {
+static const ShSet &shift_table(Device &dev, int m, const uint64_t *shift_mont, bool inverse, const uint64_t *d_ninv) {
   using F = typename Cfg::Fd;
   using HF = typename Cfg::Fh;
-  ShKey key(dev.uid * 2 + curve, m, (inverse ? 1 : 0) | (d_ninv ? 2 : 0), shift_mont[0], shift_mont[1], shift_mont[2],
-            shift_mont[3]);
+  ShKey key(dev.uid * 2 + Cfg::curve, m, (inverse ? 1 : 0) | (d_ninv ? 2 : 0), shift_mont[0], shift_mont[1],
+            shift_mont[2], shift_mont[3]);
   std::lock_guard<std::mutex> lock(g_tw_mu);
   auto it = g_sh.find(key);
   if (it != g_sh.end()) {
@@ -1044,30 +926,16 @@ static const ShSet &shift_table(Device &dev, int curve, int m, const uint64_t *s
     memcpy(&pows[(size_t)b * HF::N], s.v, sizeof s.v);
     zkh::sqr(s, s);
   }
-  auto evict_one = [&]() -> bool {  // the context's least recently used set (its stream is idle between calls)
-    auto victim = g_sh.end();
+  for (;;) {  // room for one more set of this context (its stream is idle between calls)
     size_t mine = 0;
-    for (auto i2 = g_sh.begin(); i2 != g_sh.end(); ++i2)
-      if (std::get<0>(i2->first) / 2 == dev.uid) {
-        mine++;
-        if (victim == g_sh.end() || i2->second.last_use < victim->second.last_use) victim = i2;
-      }
-    if (!mine) return false;
-    ZK_CHECK(hipStreamSynchronize(dev.stream));
-    ZK_CHECK(hipFree(victim->second.mem));
-    g_sh.erase(victim);
-    return true;
-  };
-  for (;;) {
-    size_t mine = 0;
-    for (auto &kv : g_sh) mine += std::get<0>(kv.first) / 2 == dev.uid;
-    if (mine < SH_CACHE_SETS || !evict_one()) break;
+    for_context(g_sh, dev, [&](auto) { mine++; });
+    if (mine < SH_CACHE_SETS || !evict_lru(g_sh, dev)) break;
   }
   ShSet ss;
   const size_t words = (((size_t)1 << h) + ((size_t)1 << (m - h))) * el + pows.size();
   while (hipMalloc(&ss.mem, words * 8) != hipSuccess) {
     (void)hipGetLastError();
-    ZK_REQUIRE(evict_one(), "ntt: out of device memory for the shift table");
+    ZK_REQUIRE(evict_lru(g_sh, dev), "ntt: out of device memory for the shift table");
   }
   ss.slo = ss.mem;
   ss.shi = ss.slo + ((size_t)1 << h) * el;
@@ -1086,88 +954,36 @@ static const ShSet &shift_table(Device &dev, int curve, int m, const uint64_t *s
   return g_sh.emplace(key, ss).first->second;
 }
 
-// the pass chains of `batch` transforms (rows b * 2^m of d_src, d_dst and scratch), every pass one
-// launch over all of them (or several, beyond the grid cap); d_dst may be d_src
+// the pass chains of `batch` transforms (rows b * 2^m of in, d_dst and scratch), every pass one
+// launch over all of them (or several, beyond the grid cap); d_dst may be in
 template <class Cfg>
 static void ntt_ext_passes(Device &dev, int m, const std::vector<int> &dig, const TwSet &tw, const ShSet *sh,
-                           bool inverse, size_t batch, const uint64_t *d_src, uint64_t *d_dst, uint64_t *scratch) {
-  using F = typename Cfg::Fd;
-  const size_t N = (size_t)1 << m;
-  const int P = (int)dig.size();
-  size_t S = N, T = 1;
-  const uint64_t *in = d_src;
-  hipStream_t st = dev.stream;
-  PassArgs pa;
-  pa.m = m;
-  pa.P = P;
-  for (int p = 0; p < P && p < 8; p++) pa.dig[p] = dig[p];
+                           bool inverse, size_t batch, const uint64_t *in, uint64_t *d_dst, uint64_t *scratch) {
   const unsigned cap_hook = g_ext_max_grid.load();
   const unsigned long long cap = cap_hook ? cap_hook : NTT_EXT_MAX_GRID;
-  for (int p = 0; p < P; p++) {
-    const int r = dig[p];
-    const int R = 1 << r;
-    S >>= r;
-    const int last = (p == P - 1);
-    uint64_t *out = last ? d_dst : scratch;
-    const bool big = r > 8;
-    const int tile = big ? NTT_TILE_BIG : NTT_TILE;
-    int G;  // as ntt_passes
-    if (P == 1) {
-      G = 1;
-    } else if (!last) {
-      G = tile / R;
-      if ((size_t)G > S) G = (int)S;
-    } else {
-      G = tile / R;
-      if (G > (1 << dig[0])) G = 1 << dig[0];
-    }
-    const size_t ntiles = N / ((size_t)R * G);
-    const size_t lds = (size_t)G * R * F::N * 4;
-    pa.r = r;
-    pa.S = (int)S;
-    pa.T = (int)T;
-    pa.last = last;
-    pa.G = G;
-    pa.h = tw.h;
-    pa.otf = (!last && !tw.tab[p]) ? 1 : 0;
-    ExtArgs ea;
-    ea.ntiles = (unsigned)ntiles;
-    ea.mode = !sh ? 0 : (!inverse && p == 0) ? 1 : (inverse && last) ? 2 : 0;
-    ea.sh = sh ? sh->h : 0;
-    ea.slo = sh ? sh->slo : nullptr;
-    ea.shi = sh ? sh->shi : nullptr;
-    const void *kfn =
-        big ? (const void *)k_ntt_pass_ext<F, NTT_THREADS_BIG> : (const void *)k_ntt_pass_ext<F, NTT_THREADS>;
-    ZK_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const unsigned long long total = (unsigned long long)batch * ntiles;
-    for (unsigned long long t0 = 0; t0 < total; t0 += cap) {
-      const unsigned grid = (unsigned)std::min(cap, total - t0);
-      ea.tile0 = t0;
-      if (big)
-        hipLaunchKernelGGL((k_ntt_pass_ext<F, NTT_THREADS_BIG>), dim3(grid), dim3(NTT_THREADS_BIG), lds, st, in, out,
-                           pa, tw.inner_i[p], tw.tab[p], last ? tw.scale : nullptr, tw.tlo, tw.thi, ea);
-      else
-        hipLaunchKernelGGL((k_ntt_pass_ext<F, NTT_THREADS>), dim3(grid), dim3(NTT_THREADS), lds, st, in, out, pa,
-                           tw.inner_i[p], tw.tab[p], last ? tw.scale : nullptr, tw.tlo, tw.thi, ea);
-      ZK_CHECK(hipGetLastError());
-    }
+  for (int p = 0; p < (int)dig.size(); p++) {
+    const PassArgs a = plan_pass(m, dig, p, tw);
+    uint64_t *out = a.last ? d_dst : scratch;
+    const int mode = !sh ? 0 : (!inverse && p == 0) ? 1 : (inverse && a.last) ? 2 : 0;
+    ExtArgs ea = {0, (unsigned)pass_tiles(a), mode, sh ? sh->h : 0, sh ? sh->slo : nullptr, sh ? sh->shi : nullptr};
+    const unsigned long long total = (unsigned long long)batch * ea.ntiles;
+    for (ea.tile0 = 0; ea.tile0 < total; ea.tile0 += cap)
+      launch_pass<typename Cfg::Fd, true>(dev, false, a, (unsigned)std::min(cap, total - ea.tile0), in, out, tw, p, ea);
     in = out;
-    T <<= r;
   }
 }
 
 template <class Cfg>
-static void ntt_ext_run(Device &dev, int curve, int m, const uint64_t *gen_mont, const uint64_t *shift_mont,
+static void ntt_ext_run(Device &dev, int m, const uint64_t *gen_mont, const uint64_t *shift_mont,
                         size_t batch, const uint64_t *src, uint64_t *dst, bool host_io, bool inverse) {
   using F = typename Cfg::Fd;
   const size_t N = (size_t)1 << m;
   hipStream_t st = dev.stream;
   std::vector<int> dig;
   split_digits(m, dig);
-  TwSet &tw = twiddles<Cfg>(dev, curve, m, gen_mont, inverse, dig);
+  TwSet &tw = twiddles<Cfg>(dev, m, gen_mont, inverse, dig);
   // the inverse's 1/N rides on the shift table exactly when the last pass owes it (tw.scale)
-  const ShSet *sh = shift_mont ? &shift_table<Cfg>(dev, curve, m, shift_mont, inverse, inverse ? tw.scale : nullptr)
-                               : nullptr;
+  const ShSet *sh = shift_mont ? &shift_table<Cfg>(dev, m, shift_mont, inverse, inverse ? tw.scale : nullptr) : nullptr;
 
   // working set of c transforms at a time: scratch, and the staged source and destination of the
   // host form; when it does not fit, the batch runs in contiguous chunks, halved down to one
@@ -1211,8 +1027,9 @@ int ntt_ext(int curve, int m, const uint64_t *gen_mont, const uint64_t *shift_mo
   if (batch == 0) return 0;
   Device &dev = current_device();
   std::lock_guard<std::mutex> lock(dev.mu);
-  if (curve == 0) ntt_ext_run<CfgBN>(dev, curve, m, gen_mont, shift_mont, (size_t)batch, src, dst, host_io, inverse);
-  else ntt_ext_run<CfgBLS>(dev, curve, m, gen_mont, shift_mont, (size_t)batch, src, dst, host_io, inverse);
+  with_cfg(curve, [&](auto cfg) {
+    ntt_ext_run<decltype(cfg)>(dev, m, gen_mont, shift_mont, (size_t)batch, src, dst, host_io, inverse);
+  });
   return 0;
 }
 
@@ -1221,33 +1038,24 @@ void ntt_enqueue(Device &dev, int curve, int m, const uint64_t *gen_mont, const 
   ZK_REQUIRE(m >= 0 && m <= 30, "ntt: log2 size out of range (0..30)");
   std::vector<int> dig;
   split_digits(m, dig);
-  if (curve == 0) ntt_passes<CfgBN>(dev, m, dig, twiddles<CfgBN>(dev, curve, m, gen_mont, inverse, dig), d_src, d_dst, scratch, false);
-  else ntt_passes<CfgBLS>(dev, m, dig, twiddles<CfgBLS>(dev, curve, m, gen_mont, inverse, dig), d_src, d_dst, scratch, false);
+  with_cfg(curve, [&](auto cfg) {
+    using Cfg = decltype(cfg);
+    ntt_passes<Cfg>(dev, m, dig, twiddles<Cfg>(dev, m, gen_mont, inverse, dig), d_src, d_dst, scratch, false);
+  });
 }
 
 void ntt_release(Device &dev) {
   std::lock_guard<std::mutex> lock(g_tw_mu);
-  for (auto it = g_tw.begin(); it != g_tw.end();) {
-    if (std::get<0>(it->first) / 2 == dev.uid) {
-      ZK_CHECK(hipFree(it->second.mem));
-      it = g_tw.erase(it);
-    } else {
-      ++it;
-    }
-  }
-  for (auto it = g_sh.begin(); it != g_sh.end();) {
-    if (std::get<0>(it->first) / 2 == dev.uid) {
-      ZK_CHECK(hipFree(it->second.mem));
-      it = g_sh.erase(it);
-    } else {
-      ++it;
-    }
-  }
+  drop_entries(g_tw, dev);
+  drop_entries(g_sh, dev);
 }
 
 void ntt(int curve, int m, const uint64_t *gen_mont, const uint64_t *src, uint64_t *dst, bool host_io,
          bool inverse) {
   ZK_REQUIRE(m >= 0 && m <= 30, "ntt: log2 size out of range (0..30)");
+  auto run = [&](Device &dev, const Spread *sp) {
+    with_cfg(curve, [&](auto cfg) { ntt_run<decltype(cfg)>(dev, m, gen_mont, src, dst, host_io, inverse, sp); });
+  };
   std::vector<int> set = host_io && m >= 16 ? device_set() : std::vector<int>();
   int cur = 0;
   ZK_CHECK(hipGetDevice(&cur));
@@ -1256,14 +1064,6 @@ void ntt(int curve, int m, const uint64_t *gen_mont, const uint64_t *src, uint64
     // keeps its transforms on its own GPU), else on the first listed device
     const auto it = std::find(set.begin(), set.end(), cur);
     if (it != set.end()) std::rotate(set.begin(), it, set.end());
-  }
-  if (set.size() == 1 && set[0] != cur) {  // a one-entry set pins the transform to that device
-    DeviceGuard on(set[0]);
-    Device &dev = current_device();
-    std::lock_guard<std::mutex> lock(dev.mu);
-    if (curve == 0) ntt_run<CfgBN>(dev, curve, m, gen_mont, src, dst, host_io, inverse);
-    else ntt_run<CfgBLS>(dev, curve, m, gen_mont, src, dst, host_io, inverse);
-    return;
   }
   if (set.size() > 1) {
     // compute on the first device of the (rotated) set, host I/O spread over every listed one;
@@ -1287,14 +1087,13 @@ void ntt(int curve, int m, const uint64_t *gen_mont, const uint64_t *src, uint64
       enable_peer(set[k], set[0]);
     }
     DeviceGuard on(set[0]);
-    if (curve == 0) ntt_run<CfgBN>(*ctx[0], curve, m, gen_mont, src, dst, host_io, inverse, &sp);
-    else ntt_run<CfgBLS>(*ctx[0], curve, m, gen_mont, src, dst, host_io, inverse, &sp);
+    run(*ctx[0], &sp);
     return;
   }
+  DeviceGuard on(set.size() == 1 ? set[0] : cur);  // a one-entry set pins the transform to that device
   Device &dev = current_device();
   std::lock_guard<std::mutex> lock(dev.mu);
-  if (curve == 0) ntt_run<CfgBN>(dev, curve, m, gen_mont, src, dst, host_io, inverse);
-  else ntt_run<CfgBLS>(dev, curve, m, gen_mont, src, dst, host_io, inverse);
+  run(dev, nullptr);
 }
 
 }  // namespace zk
