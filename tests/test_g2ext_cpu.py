@@ -33,7 +33,7 @@ def test_library_exports_g2ext_symbols(zk):
 def test_symbol_lists_name_g2ext(zk):
     assert set(REF_NAMES) <= set(zk.REFERENCE_SYMBOLS)
     assert set(EXT_NAMES) <= set(zk.EXTENSION_SYMBOLS)
-    for f in ("g2_batch_from_affine", "g2_batch_to_affine", "g2_msm_variable", "g2_msm_proj"):
+    for f in ("g2_batch_from_affine", "g2_batch_to_affine", "g2_msm_variable", "g2_msm_proj", "g2_msm_device"):
         assert callable(getattr(zk, f))
 
 

@@ -2,7 +2,16 @@
 (<C>_G2_proj_MSM_{mont,std}_coeff_{proj,affine}_out, bls12_381_G2_proj.c:498-660),
 bit-exact against the reference's own C (oracle/_ref).  Test points are built with the
 reference library itself: an arithmetic progression P0 + i H of generator multiples,
-converted by its batch_to_affine."""
+converted by its batch_to_affine.
+
+Which kernels these cases reach: a default-window call of at most 4096 pairs (msm_bits_max) takes
+the bit-job path (k_bitacc / k_bitsum) and never runs a bucket, a sort, a stitch level or a Y sum.
+  test_g2_msm_vs_reference (n <= 2048) and test_g2_msm_edge_cases (n = 257)   bit jobs only
+  test_g2_msm_linearity_large (2^16)   the bucket pipeline, but one GPU result against another
+  test_g2_msm_vs_reference_at_bench_sizes (2^16, 2^18)   the bucket pipeline against the reference:
+      random scalars over distinct points, so bucket runs are short and no two equal points meet
+The bucket pipeline's own cases (skewed scalars, equal and opposite points, the window sweep, window
+groups, sort-ahead, host splits, scalar widths) are in test_gpu_g2_pipeline.py."""
 import hashlib
 
 import numpy as np

@@ -339,7 +339,6 @@ def g2_msm_proj(curve, coeffs, proj_points, std=False, affine=False):
     n = coeffs.shape[0]
     coeffs = np.ascontiguousarray(coeffs, dtype=np.uint64)
     proj_points = np.ascontiguousarray(proj_points, dtype=np.uint64)
-    res = np.zeros(6 * NP, dtype=np.uint64)
     bufs = []
     try:
         bufs.append(DeviceBuffer(coeffs))
@@ -347,7 +346,7 @@ def g2_msm_proj(curve, coeffs, proj_points, std=False, affine=False):
         bufs.append(DeviceBuffer.empty(n * 4 * NP * 8))
         d_sc, d_proj, d_aff = bufs
         lib.zkg_g2_batch_to_affine_device(cid, n, d_proj.ptr, d_aff.ptr)
-        lib.zkg_g2_msm_device(cid, n, d_sc.ptr, coeffs.shape[1], 0 if std else 1, d_aff.ptr, _p(res), 0)
+        res = g2_msm_device(curve, n, d_sc, d_aff, mont=not std, nlimbs=coeffs.shape[1])
     finally:
         for b in bufs:
             b.free()
@@ -849,6 +848,14 @@ class DeviceBuffer:
 def msm_device(curve, n, d_scalars, d_points, mont=True, window=0, nlimbs=4):
     out = np.zeros(3 * NLIMBS_P[curve], dtype=np.uint64)
     load().zkg_g1_msm_device(CURVE_ID[curve], n, d_scalars.ptr, nlimbs, 1 if mont else 0, d_points.ptr, _p(out),
+                             window)
+    return out
+
+
+def g2_msm_device(curve, n, d_scalars, d_points, mont=True, window=0, nlimbs=4):
+    """device-resident G2 MSM (zkg_g2_msm_device): the normalised projective row, (0 : 1 : 0) at infinity"""
+    out = np.zeros(6 * NLIMBS_P[curve], dtype=np.uint64)
+    load().zkg_g2_msm_device(CURVE_ID[curve], n, d_scalars.ptr, nlimbs, 1 if mont else 0, d_points.ptr, _p(out),
                              window)
     return out
 
