@@ -95,6 +95,16 @@ def _fft(job, A, out):
     out[job["id"] + "__plan"] = np.array(zk.g1_fft_plan(c, m), dtype=np.int64)
 
 
+def _g2_to_affine(job, A, out):
+    out[job["id"]] = zk.g2_batch_to_affine(job["curve"], A[job["pts"]])
+
+
+def _g2_fft(job, A, out):
+    sg = zk.get_fft_subgroup(job["curve"], job["m"])
+    f = zk.g2_inverse_fft if job["inverse"] else zk.g2_forward_fft
+    out[job["id"]] = f(sg, A[job["pts"]])
+
+
 def _msm_affine(job, A, out):
     out[job["id"]] = zk.msm_affine(job["curve"], A[job["sc"]], A[job["pts"]], std=job["std"])
 
@@ -135,7 +145,8 @@ def _g2_msm_device(job, A, out):
         dp.free()
 
 
-CALLS = {"g2_msm_device": _g2_msm_device, "arr": _arr, "vanish": _vanish, "to_affine": _to_affine, "fft": _fft, "msm_affine": _msm_affine,
+CALLS = {"g2_msm_device": _g2_msm_device, "arr": _arr, "vanish": _vanish, "to_affine": _to_affine, "fft": _fft, "g2_to_affine": _g2_to_affine,
+         "g2_fft": _g2_fft, "msm_affine": _msm_affine,
          "msm_variable": _msm_variable, "msm_device": _msm_device, "g2_msm": _g2_msm}
 
 

@@ -81,12 +81,10 @@ def jacobian_points(zk, oracle, curve, n, seed, n_inf=3, affine=None):
     return out
 
 
-def g2_points(reflib, curve, n, k0=12345, k1=67890, n_inf=0, seed=0):
-    """n DISTINCT affine G2 points P0 + i H (P0 = k0 G, H = k1 G, the reference's own G2 generator,
-    scl_small, add and batch_to_affine: oracle/_ref), n_inf of them replaced by the all-0xFF
-    affine infinity at positions drawn with `seed`.  Used by the G2 tests and tools/make_golden.py."""
+def g2_proj_points(reflib, curve, n, k0=12345, k1=67890):
+    """n DISTINCT projective G2 rows P0 + i H (P0 = k0 G, H = k1 G, the reference's own G2 generator,
+    scl_small and add: oracle/_ref), as the additions leave them (Z != 1)"""
     import ctypes
-    import random
     NP = {"bn128": 4, "bls12_381": 6}[curve]
     lib = reflib
     gen = np.ctypeslib.as_array((ctypes.c_uint64 * (6 * NP)).in_dll(lib, f"{curve}_G2_proj_gen_G2")).copy()
@@ -105,6 +103,18 @@ def g2_points(reflib, curve, n, k0=12345, k1=67890, n_inf=0, seed=0):
     row = 6 * NP * 8
     for i in range(1, n):
         add(base + (i - 1) * row, hp, base + i * row)
+    return proj
+
+
+def g2_points(reflib, curve, n, k0=12345, k1=67890, n_inf=0, seed=0):
+    """g2_proj_points as n DISTINCT affine G2 points (the reference's batch_to_affine), n_inf of them
+    replaced by the all-0xFF affine infinity at positions drawn with `seed`.  Used by the G2 tests and
+    tools/make_golden.py."""
+    import ctypes
+    import random
+    NP = {"bn128": 4, "bls12_381": 6}[curve]
+    lib = reflib
+    proj = g2_proj_points(reflib, curve, n, k0, k1)
     aff = np.zeros((n, 4 * NP), np.uint64)
     f = getattr(lib, f"{curve}_G2_proj_batch_to_affine")
     f.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]

@@ -14,7 +14,7 @@ or the hooks' validation produce: they reach designed paths at small sizes (grid
 CHK up to 128, chk up to 32, K = BITACC_MAX_K, radix-8 / radix-16 Stockham stages with remainder
 stages), they do not push a kernel outside its design.
 
-test_switch_table_is_complete (no GPU) keeps the table equal to the getenv("ZK_*") calls of csrc.
+test_switch_table_is_complete (no GPU) keeps the table equal to the ZK_* switches that csrc reads.
 """
 import json
 import os
@@ -294,6 +294,83 @@ def fft_norm(ctx, bt):
     fft(ctx, bt, sizes=[3, 5])
 
 
+# ---------------------------------------------------------------------------- G2 conversion and transform (zk_g2norm.hpp's chain)
+G2_AFFINE_SIZES = [1, 2, 31, 33, 257]  # ZK_NORM_LANES=1: chk = clamp(n, 2, 32), 257 rows = 9 lanes of 28 / 29; =100: chk = 2
+
+
+def _g2_rows(ctx, curve):
+    """distinct finite projective G2 rows (Z != 1) and the infinity (0 : 1 : 0), from the reference"""
+    def make():
+        NP = ctx.gpu.NLIMBS_P[curve]
+        rows = golden_io.g2_proj_points(ctx.reference.lib, curve, max(G2_AFFINE_SIZES))
+        inf = np.zeros((1, 6 * NP), np.uint64)
+        ctx.reference.arr(curve, "G2_proj_batch_from_affine", 1, np.full((1, 4 * NP), ALL_ONES, np.uint64), inf)
+        assert rows[:, 4 * NP:].any(axis=1).all() and not inf[0, 4 * NP:].any()
+        return rows, inf[0]
+    return cached(("g2rows", curve), make)
+
+
+def g2_infinity_rows(n):
+    """rows written with Z = 0: none at n = 1 (a finite row), the first at n = 2, and from 31 rows the
+    first, the last and every row of one of the 9 strided lanes that 257 rows have under
+    ZK_NORM_LANES=1 (rows = 3 mod 9: that lane's product is 1 throughout)"""
+    if n < 2:
+        return []
+    return [0] if n == 2 else sorted({0, n - 1} | set(range(3, n, 9)))
+
+
+def g2_to_affine(ctx, bt):
+    """G2 batch_to_affine: finite rows with Z != 1 and both forms of infinity, (0 : 1 : 0) and
+    (x : y : 0), alternating over g2_infinity_rows, against the reference's G2_proj_batch_to_affine"""
+    for curve in CURVES:
+        NP = ctx.gpu.NLIMBS_P[curve]
+        rows, inf = _g2_rows(ctx, curve)
+        for n in G2_AFFINE_SIZES:
+            def make():
+                pts = rows[:n].copy()
+                for k, i in enumerate(g2_infinity_rows(n)):
+                    if k % 2 == 0:
+                        pts[i] = inf
+                    else:
+                        pts[i, 4 * NP:] = 0  # (x : y : 0)
+                w = np.zeros((n, 4 * NP), dtype=np.uint64)
+                ctx.reference.arr(curve, "G2_proj_batch_to_affine", n, pts, w)
+                fin = np.ones(n, bool)
+                fin[g2_infinity_rows(n)] = False
+                assert (w[~fin] == ALL_ONES).all() and not (w[fin] == ALL_ONES).all(axis=1).any()
+                return pts, w
+            pts, w = cached(("g2aff", curve, n), make)
+            tag = f"g2aff_{curve}_{n}"
+            bt.expect(bt.job(id=tag, call="g2_to_affine", curve=curve, pts=bt.put(tag + "_in", pts)), w)
+
+
+G2_FFT_SIZES = [0, 1, 3, 5]
+
+
+def g2_fft(ctx, bt):
+    """the G2 transform, whose closing normalisation runs the same chain on ZZZ: distinct finite rows,
+    at m = 5 with row 0 the infinity (0 : 1 : 0), against the reference's G2_proj_fft_forward / _inverse"""
+    for curve in CURVES:
+        rows, inf = _g2_rows(ctx, curve)
+        for m in G2_FFT_SIZES:
+            def make():
+                pts = rows[:1 << m].copy()
+                if m == 5:
+                    pts[0] = inf
+                gen = ctx.gpu.get_fft_subgroup(curve, m).gen_array()
+                w = {}
+                for inverse in (False, True):
+                    w[inverse] = np.zeros_like(pts)
+                    ctx.reference.arr(curve, f"G2_proj_fft_{'inverse' if inverse else 'forward'}", m, gen, pts, w[inverse])
+                return pts, w
+            pts, w = cached(("g2fft", curve, m), make)
+            kin = bt.put(f"g2fft_{curve}_{m}_in", pts)
+            for inverse in (False, True):
+                jid = bt.job(id=f"g2fft_{curve}_{m}_{'inv' if inverse else 'fwd'}", call="g2_fft", curve=curve, m=m,
+                             inverse=inverse, pts=kin)
+                bt.expect(jid, w[inverse])
+
+
 # ---------------------------------------------------------------------------- G1 MSM (zk_msm_impl.hpp)
 R_MOD = golden_io.FR_ORDER
 P_MOD = {"bn128": 21888242871839275222246405745257275088696311157297823662689037894645226208583,
@@ -566,8 +643,9 @@ def _rows():
     add({"ZK_VANISH_STAGED": "1"}, vanish)
     # batch affine conversion: the other k_norm_chunks branches, chk = clamp(n, 2, 32), chk = 10
     add({"ZK_NORM_BF": "0"}, to_affine, fft_norm, fp_edges)
-    add({"ZK_NORM_LANES": "1"}, to_affine, fft_norm, lambda ctx, bt: fp_edges(ctx, bt, chk=32))
-    add({"ZK_NORM_LANES": "100"}, to_affine, fft_norm)
+    # (the G2 conversion and transform size their shared norm chain with ZK_NORM_LANES as well)
+    add({"ZK_NORM_LANES": "1"}, to_affine, fft_norm, lambda ctx, bt: fp_edges(ctx, bt, chk=32), g2_to_affine, g2_fft)
+    add({"ZK_NORM_LANES": "100"}, to_affine, fft_norm, g2_to_affine, g2_fft)
     for flag in ("ZK_INV_SG", "ZK_INV_STRIDE", "ZK_NORM_BF"):
         add({flag: "0", "ZK_NORM_LANES": "1"}, to_affine, fft_norm)
     # group FFT: the fused radix-2 stages, radix 4 / 8 / 16 Stockham stages with remainder stages,
@@ -658,12 +736,13 @@ def test_switch(request, tmp_path, row):
 
 
 def test_switch_table_is_complete():
-    """every getenv("ZK_*") of csrc is a key of the table above or of EXCLUDED, and the table names
+    """every getenv("ZK_*") of csrc, direct or through zk_runtime.hpp's readers (env_on, env_is1,
+    env_pos, env_int), is a key of the table above or of EXCLUDED, and the table names
     no switch the code does not read: a mistyped name or a switch added without a test fails here"""
     found = set()
     for name in sorted(os.listdir(CSRC)):
         with open(os.path.join(CSRC, name), encoding="utf-8", errors="replace") as f:
-            found |= set(re.findall(r'getenv\("(ZK_[A-Z0-9_]+)"\)', f.read()))
+            found |= set(re.findall(r'\b(?:getenv|env_on|env_is1|env_pos|env_int)\("(ZK_[A-Z0-9_]+)"', f.read()))
     assert found, "no ZK_* switch found under csrc"
     assert not (TABLE_SWITCHES & set(EXCLUDED)), "a switch is both tested and excluded"
     assert found == TABLE_SWITCHES | set(EXCLUDED), (

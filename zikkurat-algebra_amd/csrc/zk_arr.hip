@@ -825,11 +825,7 @@ struct Stage {
 // 5.7-5.9 -> 5.8-6.1 (r06h_arr_pf_ab.txt, r06i); on the product ops it measured level or slower.
 // ZK_ARR_GRID overrides the cap for every op (A/B hook, read once).
 static unsigned stream_grid(size_t n, bool products = false) {
-  static const size_t cap_env = [] {
-    const char *e = getenv("ZK_ARR_GRID");
-    const long v = e ? atol(e) : 0;
-    return v > 0 ? (size_t)v : (size_t)0;
-  }();
+  static const size_t cap_env = (size_t)env_pos("ZK_ARR_GRID", 0);
   const size_t cap = cap_env ? cap_env : (products ? (size_t)8192 : (size_t)1 << 30);
   size_t b = (n + 255) / 256;
   if (b > cap) b = cap;
@@ -841,15 +837,9 @@ static bool arr_op_has_product(int op) {
 }
 template <class F>
 static void launch_arr_op(int op, const ArrArgs &g, dim3 grid, hipStream_t st) {
-  static const int stage_env = [] {
-    const char *e = getenv("ZK_ARR_STAGE");
-    return e ? atoi(e) : -1;
-  }();
+  static const int stage_env = env_int("ZK_ARR_STAGE", -1);  // unset: the per-op default below
   const int stage = stage_env >= 0 ? stage_env : (arr_op_has_product(op) ? 2 : 4);
-  static const bool legacy = [] {
-    const char *e = getenv("ZK_ARR_MAP");
-    return e && e[0] == '1';
-  }();
+  static const bool legacy = env_is1("ZK_ARR_MAP");
   if (legacy) {
     hipLaunchKernelGGL(k_arr_map<F>, grid, dim3(256), 0, st, g);
     ZK_CHECK(hipGetLastError());
@@ -907,32 +897,19 @@ static void arr_op_t(Device &dev, int op, int n, const uint64_t *a, const uint64
       // N / CHK are sized to ZK_INV_LANES (default 131072: two wavefronts per SIMD at 164 VGPRs),
       // CHK within [8, 128] (2^24: 128 -> 8.5 products per element instead of 16 at CHK 32; inv
       // 2.64 -> 1.94 ms, div 2.35 -> 1.86 ms through the host wrapper, profiles/r05u_*)
-      static const size_t inv_lanes = [] {
-        const char *e = getenv("ZK_INV_LANES");
-        const long v = e ? atol(e) : 0;
-        return v > 0 ? (size_t)v : (size_t)131072;
-      }();
+      static const size_t inv_lanes = (size_t)env_pos("ZK_INV_LANES", 131072);
       const size_t cq = N / inv_lanes;
       const int CHK = cq < 8 ? 8 : (cq > 128 ? 128 : (int)cq);
       uint64_t *scratch = dev.arena.take<uint64_t>(N * 4);
       uint32_t *flag = dev.arena.take<uint32_t>(1);
       ZK_CHECK(hipMemsetAsync(flag, 0, 4, st));
       const size_t lanes = (N + CHK - 1) / CHK;
-      static const bool sg = [] {
-        const char *e = getenv("ZK_INV_SG");
-        return !(e && e[0] == '0');
-      }();
-      static const bool strided = [] {
-        const char *e = getenv("ZK_INV_STRIDE");
-        return !(e && e[0] == '0');
-      }();
+      static const bool sg = env_on("ZK_INV_SG");
+      static const bool strided = env_on("ZK_INV_STRIDE");
       const dim3 ig(div_up(lanes, 256)), ib(256);
       const uint64_t *xs = op == ARR_DIV ? db : da;
       const U256 pm2 = p_minus_2<Cfg>();
-      static const bool ilp2 = [] {
-        const char *e = getenv("ZK_INV_ILP");
-        return !(e && e[0] == '0');
-      }();
+      static const bool ilp2 = env_on("ZK_INV_ILP");
       if (sg && strided && ilp2)
         hipLaunchKernelGGL(k_inv_chunks2<F>, ig, ib, 0, st, op, n, CHK, op == ARR_DIV ? da : xs, xs, scratch, dt, flag, (int)lanes);
       else if (sg && strided)
@@ -1064,10 +1041,7 @@ static int div_vanishing_t(Device &dev, int n1, const uint64_t *src, int n, cons
   ZK_REQUIRE(nquot >= deg - n + 1, "poly_div_by_vanishing: quotient buffer too small");  // poly_mont.c:328
   ZK_REQUIRE(!want_rem || nrem >= n, "poly_div_by_vanishing: remainder buffer too small");  // :329
   const U256 e = load_u256(eta);
-  static const bool legacy = [] {  // ZK_VANISH_LEGACY=1: the round-5 kernels (A/B hook, read once)
-    const char *v = getenv("ZK_VANISH_LEGACY");
-    return v && v[0] == '1';
-  }();
+  static const bool legacy = env_is1("ZK_VANISH_LEGACY");  // =1: the round-5 kernels (A/B hook, read once)
   // the fused kernel writes quot[0, deg - n] and rem[0, n): only the tails are cleared
   const size_t qw = (deg >= n && !legacy) ? (size_t)(deg - n + 1) : 0, rw = (deg >= n && !legacy) ? (size_t)n : 0;
   if ((size_t)nquot > qw) ZK_CHECK(hipMemsetAsync(dq + qw * 4, 0, ((size_t)nquot - qw) * 32, st));
@@ -1086,10 +1060,7 @@ static int div_vanishing_t(Device &dev, int n1, const uint64_t *src, int n, cons
     } else {
       // per-lane 32-B accesses by default: 0.186 vs 0.197 ms for the LDS-staged runs at deg 3 x 2^22
       // (profiles/r06r_vanish_prof.txt); ZK_VANISH_STAGED=1 selects those (A/B hook, read once)
-      static const bool staged = [] {
-        const char *v = getenv("ZK_VANISH_STAGED");
-        return v && v[0] == '1';
-      }();
+      static const bool staged = env_is1("ZK_VANISH_STAGED");
       if (staged) hipLaunchKernelGGL((k_vanish_fused<F, true>), dim3(div_up(n, 256)), dim3(256), 0, st, deg, n, da, e, dq, dr);
       else hipLaunchKernelGGL((k_vanish_fused<F, false>), dim3(div_up(n, 256)), dim3(256), 0, st, deg, n, da, e, dq, dr);
     }

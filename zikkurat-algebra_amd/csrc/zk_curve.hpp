@@ -16,24 +16,28 @@
 
 namespace zk {
 
-// curve descriptors: base field, scalar field, and the constants we need
+// curve descriptors: base field, scalar field, and the constants we need (ID: the C ABI's curve index)
 struct BN254 {
+  static constexpr int ID = 0;
   using Fp = BN_Fp;
   using Fr = BN_Fr;
   static constexpr int NP64 = ZK_BN128_FP_N64;
 };
 struct BLS381 {
+  static constexpr int ID = 1;
   using Fp = BLS_Fp;
   using Fr = BLS_Fr;
   static constexpr int NP64 = ZK_BLS12_381_FP_N64;
 };
 // G2: the twists over Fp2 (a = 0 as well; the XYZZ formulas never use b)
 struct BN254_G2 {
+  static constexpr int ID = 0;
   using Fp = F2<BN_Fp>;
   using Fr = BN_Fr;
   static constexpr int NP64 = 2 * ZK_BN128_FP_N64;
 };
 struct BLS381_G2 {
+  static constexpr int ID = 1;
   using Fp = F2<BLS_Fp>;
   using Fr = BLS_Fr;
   static constexpr int NP64 = 2 * ZK_BLS12_381_FP_N64;

@@ -36,12 +36,17 @@
 // one table add).
 // Outputs are normalised (Z = 1, infinity = (0:1:0)) as the reference does (:719, :785).
 // The integer stages' device routines (k_fft_load, xyzz_scl, k_fft_fwd_stage / k_fft_inv_stage) live in
-// zk_fftdev.hpp, which the G2 transform (zk_g2fft.hip) shares.
+// zk_fftdev.hpp, which the G2 transform (zk_g2fft.hip) shares.  Host side: the entry points go through
+// the curve dispatch of zk_dispatch.hpp (with_g1) and the staged host I/O and switch readers of
+// zk_runtime.hpp (StagedIO, env_on / env_pos); the transform is G1Fft<C> (sizes, twiddles, the three
+// stage runners) with SubgroupTest beside it.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 #include "zk_curve.hpp"
+#include "zk_dispatch.hpp"
 #include "zk_extdev.hpp"
 #include "zk_fftdev.hpp"
 #include "zk_host.hpp"
@@ -528,6 +533,15 @@ __device__ __forceinline__ void glv_scl_pair(Xyzz<F> &t, const Xyzz<F> &v, const
   jac_to_xyzz(t, r);
 }
 
+// what every GLV stage kernel starts with: beta in internal form, and the lane's table slot in scratch
+template <class F>
+__device__ __forceinline__ uint32_t *glv_lane_setup(Fe<F> &beta, const W6 &beta_ref, uint32_t *__restrict__ scratch) {
+  Fe<F> t0;
+  fe_load_ref(t0, beta_ref.w);
+  fe_to_int(beta, t0);
+  return scratch + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * scl_tab_words<F>();
+}
+
 // forward DIT stage on lane pairs: pair = butterfly; lane 0 writes u + t, lane 1 u - t
 template <class C>
 __global__ void __launch_bounds__(256, fft_waves<C>()) k_fft_fwd_stage_glv(int m, int s, const uint32_t *__restrict__ A,
@@ -536,10 +550,8 @@ __global__ void __launch_bounds__(256, fft_waves<C>()) k_fft_fwd_stage_glv(int m
   using F = typename C::Fp;
   const int half = 1 << (s - 1);
   const size_t nl = (size_t)1 << m;  // two lanes per butterfly
-  Fe<F> beta, t0;
-  fe_load_ref(t0, beta_ref.w);
-  fe_to_int(beta, t0);
-  uint32_t *tab = scratch + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * scl_tab_words<F>();
+  Fe<F> beta;
+  uint32_t *tab = glv_lane_setup(beta, beta_ref, scratch);
   for (size_t L = (size_t)blockIdx.x * blockDim.x + threadIdx.x; L < nl; L += (size_t)lanes) {
     const size_t b = L >> 1;
     const int q = (int)(L & 1);
@@ -569,10 +581,8 @@ __global__ void __launch_bounds__(256, fft_waves<C>()) k_fft_inv_stage_glv(int m
   using F = typename C::Fp;
   const int half = 1 << (s - 1);
   const size_t nl = (size_t)1 << m;
-  Fe<F> beta, t0;
-  fe_load_ref(t0, beta_ref.w);
-  fe_to_int(beta, t0);
-  uint32_t *tab = scratch + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * scl_tab_words<F>();
+  Fe<F> beta;
+  uint32_t *tab = glv_lane_setup(beta, beta_ref, scratch);
   for (size_t L = (size_t)blockIdx.x * blockDim.x + threadIdx.x; L < nl; L += (size_t)lanes) {
     const size_t b = L >> 1;
     const int q = (int)(L & 1);
@@ -609,10 +619,8 @@ __global__ void __launch_bounds__(256, fft_waves<C>()) k_fft_inv_first_glv(int m
   using F = typename C::Fp;
   const size_t half = (size_t)1 << (m - 1);
   const size_t nl = (size_t)1 << (m + 1);  // 4 lanes x N / 2 butterflies
-  Fe<F> beta, t0;
-  fe_load_ref(t0, beta_ref.w);
-  fe_to_int(beta, t0);
-  uint32_t *tab = scratch + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * scl_tab_words<F>();
+  Fe<F> beta;
+  uint32_t *tab = glv_lane_setup(beta, beta_ref, scratch);
   for (size_t L = (size_t)blockIdx.x * blockDim.x + threadIdx.x; L < nl; L += (size_t)lanes) {
     const size_t j = L >> 2;  // s = m: one block, k0 = j
     const int pr = (int)((L >> 1) & 1);
@@ -664,10 +672,8 @@ __global__ void __launch_bounds__(256, fft_waves<C>()) k_fft_radix_prod(int m, i
   const int b = plan.b;
   const size_t N = (size_t)1 << m, NG = N >> b, G = (size_t)1 << lgG;
   const size_t nl = 2 * NG * (size_t)plan.D;  // two lanes per product
-  Fe<F> beta, t0;
-  fe_load_ref(t0, beta_ref.w);
-  fe_to_int(beta, t0);
-  uint32_t *tab = scratch + ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * scl_tab_words<F>();
+  Fe<F> beta;
+  uint32_t *tab = glv_lane_setup(beta, beta_ref, scratch);
   for (size_t L = (size_t)blockIdx.x * blockDim.x + threadIdx.x; L < nl; L += (size_t)lanes) {
     const size_t pair = L >> 1;
     const int q = (int)(L & 1);
@@ -859,6 +865,13 @@ static W6 one_ref() {
   return o;
 }
 
+// fn(std::true_type) or fn(std::false_type): a runtime flag as a template argument (the Jacobian twins)
+template <class Fn>
+static void with_flag(bool on, Fn fn) {
+  if (on) fn(std::true_type{});
+  else fn(std::false_type{});
+}
+
 template <class C>
 static void batch_from_affine_t(Device &dev, int n, const uint64_t *src, uint64_t *tgt, bool host_io, bool jac) {
   using HF = typename HostOf<C>::Fp;
@@ -868,19 +881,13 @@ static void batch_from_affine_t(Device &dev, int n, const uint64_t *src, uint64_
   const size_t N = (size_t)n;
   dev.arena.reserve(N * 5 * NP * 8 + (1 << 20));
   dev.arena.reset();
-  const uint64_t *ds = src;
-  uint64_t *dt = tgt;
-  if (host_io) {
-    uint64_t *a = dev.arena.take<uint64_t>(N * 2 * NP);
-    ZK_CHECK(hipMemcpyAsync(a, src, N * 2 * NP * 8, hipMemcpyHostToDevice, st));
-    ds = a;
-    dt = dev.arena.take<uint64_t>(N * 3 * NP);
-  }
-  if (jac) hipLaunchKernelGGL((k_from_affine<C, true>), dim3(div_up(N, 256)), dim3(256), 0, st, n, ds, dt, one_ref<HF>());
-  else hipLaunchKernelGGL((k_from_affine<C, false>), dim3(div_up(N, 256)), dim3(256), 0, st, n, ds, dt, one_ref<HF>());
+  StagedIO io(dev, host_io, src, N * 2 * NP, tgt, N * 3 * NP);
+  with_flag(jac, [&](auto J) {
+    hipLaunchKernelGGL((k_from_affine<C, decltype(J)::value>), dim3(div_up(N, 256)), dim3(256), 0, st, n, io.in, io.out,
+                       one_ref<HF>());
+  });
   ZK_CHECK(hipGetLastError());
-  if (host_io) copy_to_host(dev, st, tgt, dt, N * 3 * NP * 8);  // fresh caller arrays: zk_runtime.hpp
-  ZK_CHECK(hipStreamSynchronize(st));
+  io.finish();
 }
 
 // points per Fermat inversion in k_norm_chunks: each lane's chain is CHK prefix products, one
@@ -892,26 +899,17 @@ static void batch_from_affine_t(Device &dev, int n, const uint64_t *src, uint64_
 // 4, 0.528 at 2, 0.553 at 1.
 // ZK_INV_SG=0: Fermat inversions in k_norm_chunks (A/B hook, read once; default: safegcd)
 static bool inv_sg() {
-  static const bool on = [] {
-    const char *e = getenv("ZK_INV_SG");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("ZK_INV_SG");
   return on;
 }
 // ZK_INV_STRIDE=0: consecutive-point chunks (A/B hook, read once; default strided)
 static bool inv_strided() {
-  static const bool on = [] {
-    const char *e = getenv("ZK_INV_STRIDE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("ZK_INV_STRIDE");
   return on;
 }
 // ZK_NORM_BF=0: k_norm_chunks with the round-6 branches (A/B hook, read once; default branch-free)
 static bool norm_bf() {
-  static const bool on = [] {
-    const char *e = getenv("ZK_NORM_BF");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("ZK_NORM_BF");
   return on;
 }
 template <class C, int MODE>
@@ -934,11 +932,7 @@ static void launch_norm(hipStream_t st, int n, int chk, const void *src, uint64_
   ZK_CHECK(hipGetLastError());
 }
 int norm_chk(size_t N) {
-  static const size_t target = [] {
-    const char *e = getenv("ZK_NORM_LANES");
-    const long v = e ? atol(e) : 0;
-    return v > 0 ? (size_t)v : (size_t)65536;
-  }();
+  static const size_t target = (size_t)env_pos("ZK_NORM_LANES", 65536);
   const size_t c = N / target;
   return c < 2 ? 2 : (c > 32 ? 32 : (int)c);
 }
@@ -952,23 +946,13 @@ static void batch_to_affine_t(Device &dev, int n, const uint64_t *src, uint64_t 
   const size_t N = (size_t)n;
   dev.arena.reserve(N * 6 * NP * 8 + (1 << 20));
   dev.arena.reset();
-  const uint64_t *ds = src;
-  uint64_t *dt = tgt;
-  if (host_io) {
-    uint64_t *a = dev.arena.take<uint64_t>(N * 3 * NP);
-    ZK_CHECK(hipMemcpyAsync(a, src, N * 3 * NP * 8, hipMemcpyHostToDevice, st));
-    ds = a;
-    dt = dev.arena.take<uint64_t>(N * 2 * NP);
-  }
+  StagedIO io(dev, host_io, src, N * 3 * NP, tgt, N * 2 * NP);
   uint64_t *scratch = dev.arena.take<uint64_t>(N * NP);
-  const int chk = norm_chk(N);
-  if (jac)
-    launch_norm<C, MODE_JAC_TO_AFF>(st, n, chk, ds, scratch, dt, exp_p_minus_2<HF>(), 0);
-  else
-    launch_norm<C, MODE_PROJ_TO_AFF>(st, n, chk, ds, scratch, dt, exp_p_minus_2<HF>(), 0);
-  ZK_CHECK(hipGetLastError());
-  if (host_io) copy_to_host(dev, st, tgt, dt, N * 2 * NP * 8);
-  ZK_CHECK(hipStreamSynchronize(st));
+  with_flag(jac, [&](auto J) {
+    launch_norm<C, decltype(J)::value ? MODE_JAC_TO_AFF : MODE_PROJ_TO_AFF>(st, n, norm_chk(N), io.in, scratch, io.out,
+                                                                            exp_p_minus_2<HF>(), 0);
+  });
+  io.finish();
 }
 
 static RadixPlan make_radix_plan(int b, bool scaled) {
@@ -1021,10 +1005,7 @@ static double stage_rounds(double waves, int waves_per_simd) {
   return waves <= 1024.0 ? 1.0 : 1.75 * std::ceil(waves / 2048.0);
 }
 static std::vector<int> radix_plan(int m, int waves_per_simd) {
-  static const int forced = [] {
-    const char *e = getenv("ZK_FFT_RADIX");
-    return e ? atoi(e) : 0;
-  }();
+  static const int forced = env_int("ZK_FFT_RADIX", 0);
   std::vector<int> bits;
   if (forced == 1) return bits;
   if (forced >= 2 && forced <= 4) {
@@ -1077,101 +1058,22 @@ static void int_twiddles_t(hipStream_t st, const uint64_t *gen, bool inverse, si
   ZK_CHECK(hipGetLastError());
 }
 void fft_int_twiddles(int curve, hipStream_t st, const uint64_t *gen, bool inverse, size_t cnt, uint64_t *tw) {
-  if (curve == 0) int_twiddles_t<BN254>(st, gen, inverse, cnt, tw);
-  else int_twiddles_t<BLS381>(st, gen, inverse, cnt, tw);
+  on_curve<BN254, BLS381>(curve, [&](auto c) { int_twiddles_t<decltype(c)>(st, gen, inverse, cnt, tw); });
 }
 
-template <class C>
-static void g1_fft_t(Device &dev, int m, const uint64_t *gen, const uint64_t *src, uint64_t *tgt, bool host_io,
-                     bool inverse, bool jac) {
-  using F = typename C::Fp;
-  using HF = typename HostOf<C>::Fp;
-  using HR = typename HostOf<C>::Fr;
-  using Fr = typename C::Fr;
-  constexpr int NP = C::NP64;
-  ZK_REQUIRE(m >= 0 && m <= 26, "G1 fft: log2 size out of range (0..26)");
-  hipStream_t st = dev.stream;
-  const size_t N = (size_t)1 << m;
-  // scalar-multiplication lanes are grid-strided so the per-lane table scratch stays bounded.
-  // (Round 4 measured quad-cooperative stages -- 4 lanes per multiplication, signed 5-bit
-  // windows, xyzz_dbl_quad / xyzz_add_quad: BLS12-381 2^16 forward 50 vs 55 ms, inverse 102 vs
-  // 61 ms; at 1-2 waves per SIMD the quads' 4x lanes take extra rounds, profiles/r04g_*.)
-  const size_t work = inverse ? N : N / 2;
-  size_t lanes = work < (1u << 17) ? work : (1u << 17);
-  lanes = (lanes + 255) & ~(size_t)255;
-  if (lanes == 0) lanes = 256;
-  const size_t tw_cnt = N > 1 ? N / 2 : 1;
-  // GLV stages: two lanes per multiplication (forward N / 2 butterflies, inverse N / 2 plus the
-  // final N^-1 scaling of N points)
-  size_t glanes = N < (1u << 17) ? N : (1u << 17);
-  glanes = (glanes + 255) & ~(size_t)255;
-  // radix-2^b stages (GLV path only, m > 0)
-  const std::vector<int> rbits = m > 0 ? radix_plan(m, fft_waves<C>()) : std::vector<int>();
-  const bool radix = !rbits.empty();
-  size_t rlanes = 0, pbuf = 0;
-  if (radix)
-    for (int b : rbits) {
-      const size_t np = (size_t)(make_radix_plan(b, true).D) * (N >> b);
-      rlanes = std::max(rlanes, std::min(2 * np, (size_t)1 << 17));
-      pbuf = std::max(pbuf, np);
-    }
-  rlanes = (rlanes + 255) & ~(size_t)255;
-  const size_t tlanes = std::max(std::max(lanes, glanes), rlanes);
-  const size_t nbad = div_up(N, 256);
-  dev.arena.reserve(N * 3 * NP * 8 * (host_io ? 2 : 0) + 3 * N * xw<F>() * 4 + tlanes * scl_tab_words<F>() * 4 +
-                    tw_cnt * 32 + 2 * tw_cnt * 64 + 64 + nbad * 4 + N * NP * 8 + pbuf * xw<F>() * 4 + (1 << 20));
-  dev.arena.reset();
-  const uint64_t *ds = src;
-  uint64_t *dt = tgt;
-  if (host_io) {
-    uint64_t *a = dev.arena.take<uint64_t>(N * 3 * NP);
-    ZK_CHECK(hipMemcpyAsync(a, src, N * 3 * NP * 8, hipMemcpyHostToDevice, st));
-    ds = a;
-    dt = dev.arena.take<uint64_t>(N * 3 * NP);
-  }
-  uint32_t *A = dev.arena.take<uint32_t>(N * xw<F>());
-  uint32_t *B = dev.arena.take<uint32_t>(N * xw<F>());
-  uint32_t *scratch = dev.arena.take<uint32_t>(tlanes * scl_tab_words<F>());
-  uint64_t *tw = dev.arena.take<uint64_t>(tw_cnt * 4);
-  uint64_t *twg = dev.arena.take<uint64_t>(2 * tw_cnt * 8 + 8);  // w^e, then (w^-1)^e N^-1, then N^-1
-  uint32_t *bad = dev.arena.take<uint32_t>(nbad);
-  uint64_t *nscratch = dev.arena.take<uint64_t>(N * NP);
-  uint32_t *Pb = radix ? dev.arena.take<uint32_t>(pbuf * xw<F>()) : nullptr;
+// lanes of a grid-strided stage with `work` of them to do: at most 2^17 so that the per-lane table
+// scratch stays bounded, in whole workgroups, at least one
+static size_t fft_lanes(size_t work) {
+  return std::max((std::min(work, (size_t)1 << 17) + 255) & ~(size_t)255, (size_t)256);
+}
 
-  // input order: bit-reversed for the radix-2 forward stages, natural for the inverse (DIF) and the
-  // Stockham radix-2^b stages
-  auto load_points = [&](bool natural) {
-    const int br = (inverse || natural) ? 0 : m;
-    if (jac)
-      hipLaunchKernelGGL((k_fft_load<C, true>), dim3(div_up(N, 256)), dim3(256), 0, st, (int)N, br, ds, A);
-    else
-      hipLaunchKernelGGL((k_fft_load<C, false>), dim3(div_up(N, 256)), dim3(256), 0, st, (int)N, br, ds, A);
-    ZK_CHECK(hipGetLastError());
-  };
-  static const bool glv_on0 = [] {
-    const char *e = getenv("ZK_FFT_GLV");
-    return !(e && e[0] == '0');
-  }();
-  const bool use_radix = radix && glv_on0;
-  load_points(use_radix);
-  // GLV stages when every point is in the order-r subgroup (always on BN254, cofactor 1; checked
-  // on BLS12-381).  ZK_FFT_GLV=0: the integer stages always (A/B hook, read once).
-  static const bool glv_on = [] {
-    const char *e = getenv("ZK_FFT_GLV");
-    return !(e && e[0] == '0');
-  }();
-  bool glv = glv_on && m > 0;
-  const GlvParams gp = glv_params<C>();
-  const W6 beta = glv_beta_ref<C>();
-  // BLS12-381: the membership test runs on the context's side stream, on a copy of the loaded
-  // points, BESIDE the GLV stages (speculative: both are one chain per lane at <= one wavefront
-  // per SIMD up to 2^16, so they share the SIMDs' issue slots; before round 5 the stages waited
-  // for it, ~1.2 ms of a 26 ms 2^16 transform).  A point outside the subgroup (the result is
-  // read after the stages) discards the GLV result and reruns the integer stages from the input.
-  uint32_t *hb = nullptr;
-  unsigned cgrid = 0;
+// Speculative subgroup test of BLS12-381 inputs: it runs on the context's side stream, on a copy of the
+// loaded points, BESIDE the GLV stages (both are one chain per lane at <= one wavefront per SIMD up to
+// 2^16, so they share the SIMDs' issue slots; before round 5 the stages waited for it, ~1.2 ms of a
+// 26 ms 2^16 transform).  launch() enqueues it, passed() reads the verdict after the stages.
+struct SubgroupTest {
   // Every exit path -- a throw from the stages or the fallback in recoverable error mode included --
-  // waits for the side stream's test and its copy into the pinned staging before this call returns,
+  // waits for the side stream's test and its copy into the pinned staging before the call returns,
   // so no late copy can land in the next call's staging or arena.
   struct AuxJoin {
     hipStream_t s = nullptr;
@@ -1179,7 +1081,13 @@ static void g1_fft_t(Device &dev, int m, const uint64_t *gen, const uint64_t *sr
       if (s) (void)hipStreamSynchronize(s);
     }
   } aux_join;
-  if (glv && C::NP64 == 6) {
+  uint32_t *hb = nullptr;  // per-block verdicts in pinned staging; null: no test launched
+  unsigned grid = 0;
+
+  template <class C>
+  void launch(Device &dev, size_t N, size_t lanes, const uint32_t *A, const W6 &beta, uint32_t *bad) {
+    using F = typename C::Fp;
+    hipStream_t st = dev.stream;
     uint32_t *Acopy = dev.arena.take<uint32_t>(N * xw<F>());
     ZK_CHECK(hipMemcpyAsync(Acopy, A, N * xw<F>() * 4, hipMemcpyDeviceToDevice, st));
     hipEvent_t loaded = dev.split_event(0), checked = dev.split_event(1);
@@ -1187,32 +1095,96 @@ static void g1_fft_t(Device &dev, int m, const uint64_t *gen, const uint64_t *sr
     hipStream_t st2 = dev.aux_stream();
     ZK_CHECK(hipStreamWaitEvent(st2, loaded, 0));
     aux_join.s = st2;
-    cgrid = (unsigned)(glanes / 256);
-    hipLaunchKernelGGL(k_subgroup_check<C>, dim3(cgrid), dim3(256), 0, st2, (int)N, Acopy, beta, (int)glanes, bad);
+    grid = (unsigned)(lanes / 256);
+    hipLaunchKernelGGL(k_subgroup_check<C>, dim3(grid), dim3(256), 0, st2, (int)N, Acopy, beta, (int)lanes, bad);
     ZK_CHECK(hipGetLastError());
-    hb = reinterpret_cast<uint32_t *>(dev.host_staging(cgrid * 4 + 64));
-    ZK_CHECK(hipMemcpyAsync(hb, bad, cgrid * 4, hipMemcpyDeviceToHost, st2));
+    hb = reinterpret_cast<uint32_t *>(dev.host_staging(grid * 4 + 64));
+    ZK_CHECK(hipMemcpyAsync(hb, bad, grid * 4, hipMemcpyDeviceToHost, st2));
     ZK_CHECK(hipEventRecord(checked, st2));
   }
-  // Stockham radix-2^b stages (natural order in and out)
-  auto run_radix = [&] {
+  // true when every point lies in the order-r subgroup (or no test was launched)
+  bool passed(Device &dev) {
+    if (!hb) return true;
+    const hipEvent_t checked = dev.split_event(1);
+    for (;;) {
+      const hipError_t e = hipEventQuery(checked);
+      if (e == hipSuccess) break;
+      if (e != hipErrorNotReady) ZK_CHECK(e);
+      std::this_thread::yield();
+    }
+    bool ok = true;
+    for (unsigned i = 0; i < grid; i++) ok = ok && hb[i] == 0;
+    return ok;
+  }
+};
+
+// One transform's sizes, buffers and stage runners.  Each runner enqueues its twiddles and stages on
+// `st` and returns the buffer that holds the result.
+template <class C>
+struct G1Fft {
+  using F = typename C::Fp;
+  using HR = typename HostOf<C>::Fr;
+  using Fr = typename C::Fr;
+  hipStream_t st;
+  int m;
+  const uint64_t *gen;
+  bool inverse;
+  size_t N, tw_cnt;
+  // lanes of the integer stages (one per multiplication: N / 2 forward, N inverse) and of the GLV
+  // stages (two per multiplication).  (Round 4 measured quad-cooperative stages -- 4 lanes per
+  // multiplication, signed 5-bit windows, xyzz_dbl_quad / xyzz_add_quad: BLS12-381 2^16 forward 50 vs
+  // 55 ms, inverse 102 vs 61 ms; at 1-2 waves per SIMD the quads' 4x lanes take extra rounds,
+  // profiles/r04g_*.)
+  size_t lanes, glanes;
+  std::vector<int> rbits;  // radix-2^b stages (GLV path only, m > 0); empty: the fused radix-2 stages
+  size_t rlanes = 0, pbuf = 0;
+  uint32_t *A = nullptr, *B = nullptr, *scratch = nullptr, *Pb = nullptr;
+  uint64_t *tw = nullptr, *twg = nullptr;  // twg: w^e, then (w^-1)^e N^-1, then N^-1 (decomposed)
+  W6 beta = glv_beta_ref<C>();
+
+  G1Fft(hipStream_t st_, int m_, const uint64_t *gen_, bool inverse_)
+      : st(st_), m(m_), gen(gen_), inverse(inverse_), N((size_t)1 << m_), tw_cnt(N > 1 ? N / 2 : 1),
+        lanes(fft_lanes(inverse_ ? N : N / 2)), glanes(fft_lanes(N)) {
+    if (m > 0) rbits = radix_plan(m, fft_waves<C>());
+    for (int b : rbits) {
+      const size_t np = (size_t)(make_radix_plan(b, true).D) * (N >> b);
+      rlanes = std::max(rlanes, fft_lanes(2 * np));
+      pbuf = std::max(pbuf, np);
+    }
+  }
+
+  // The GLV stages' twiddles, decomposed: twg[e] = w^e forward, (w^-1)^e inverse; for the inverse also
+  // twn[e] = (w^-1)^e N^-1 behind them -- the 1/2 per level is deferred to one multiplication by N^-1
+  // folded into the first stage (on the subgroup the m halvings = N^-1) -- and, where asked for, dkn =
+  // N^-1 itself behind those.  Returns twn.
+  uint64_t *glv_twiddles(bool with_dkn) {
+    const GlvParams gp = glv_params<C>();
     zkh::Fe<HR> g, one, ninv;
     memcpy(g.v, gen, sizeof g.v);
     zkh::set_one(one);
     if (inverse) zkh::inv(g, g);
     W6 wb = {{0, 0, 0, 0, 0, 0}}, ws = {{0, 0, 0, 0, 0, 0}}, wn = {{0, 0, 0, 0, 0, 0}};
     for (int j = 0; j < 4; j++) { wb.w[j] = g.v[j]; ws.w[j] = one.v[j]; }
-    hipLaunchKernelGGL(k_fft_tw_glv<Fr>, dim3(div_up(tw_cnt, 256)), dim3(256), 0, st, (int)tw_cnt, wb, ws, gp, twg);
-    ZK_CHECK(hipGetLastError());
+    auto launch = [&](size_t cnt, const W6 &scale, uint64_t *out) {
+      hipLaunchKernelGGL(k_fft_tw_glv<Fr>, dim3(div_up(cnt, 256)), dim3(256), 0, st, (int)cnt, wb, scale, gp, out);
+      ZK_CHECK(hipGetLastError());
+    };
+    launch(tw_cnt, ws, twg);
     uint64_t *twn = twg + tw_cnt * 8;
-    if (inverse) {  // N^-1 folded into the first stage's scalars
+    if (inverse) {
       zkh::Fe<HR> nn = one;
       for (int k = 0; k < m; k++) zkh::add(nn, nn, nn);
       zkh::inv(ninv, nn);
       for (int j = 0; j < 4; j++) wn.w[j] = ninv.v[j];
-      hipLaunchKernelGGL(k_fft_tw_glv<Fr>, dim3(div_up(tw_cnt, 256)), dim3(256), 0, st, (int)tw_cnt, wb, wn, gp, twn);
-      ZK_CHECK(hipGetLastError());
+      launch(tw_cnt, wn, twn);
+      if (with_dkn) launch(1, wn, twg + 2 * tw_cnt * 8);
     }
+    return twn;
+  }
+
+  // Stockham radix-2^b stages (natural order in and out); the inverse's first stage is the scaled one
+  uint32_t *run_radix() {
+    uint64_t *twn = glv_twiddles(false);
     uint32_t *in = A, *out = B;
     int done = 0;  // log2 L
     for (size_t i = 0; i < rbits.size(); i++) {
@@ -1220,9 +1192,7 @@ static void g1_fft_t(Device &dev, int m, const uint64_t *gen, const uint64_t *sr
       const bool scaled = inverse && i == 0;
       const RadixPlan pl = make_radix_plan(b, scaled);
       const int lgG = m - done - b;
-      const size_t np = (size_t)pl.D * (N >> b);
-      size_t pl_lanes = std::min(2 * np, (size_t)1 << 17);
-      pl_lanes = (pl_lanes + 255) & ~(size_t)255;
+      const size_t pl_lanes = fft_lanes(2 * (size_t)pl.D * (N >> b));
       hipLaunchKernelGGL(k_fft_radix_prod<C>, dim3((unsigned)(pl_lanes / 256)), dim3(256), 0, st, m, lgG, in, Pb,
                          scaled ? twn : twg, scaled ? 1 : 0, beta, scratch, (int)pl_lanes, pl);
       ZK_CHECK(hipGetLastError());
@@ -1233,125 +1203,126 @@ static void g1_fft_t(Device &dev, int m, const uint64_t *gen, const uint64_t *sr
       done += b;
     }
     return in;
-  };
-  auto run_glv = [&] {
-    // twiddles (decomposed): forward w^e; inverse (w^-1)^e with the 1/2 per level deferred to one
-    // multiplication by N^-1 folded into the first stage (on the subgroup the m halvings = N^-1)
-    zkh::Fe<HR> g, one, ninv;
-    memcpy(g.v, gen, sizeof g.v);
-    zkh::set_one(one);
-    if (inverse) zkh::inv(g, g);
-    W6 wb = {{0, 0, 0, 0, 0, 0}}, ws = {{0, 0, 0, 0, 0, 0}}, wn = {{0, 0, 0, 0, 0, 0}};
-    for (int j = 0; j < 4; j++) { wb.w[j] = g.v[j]; ws.w[j] = one.v[j]; }
-    hipLaunchKernelGGL(k_fft_tw_glv<Fr>, dim3(div_up(tw_cnt, 256)), dim3(256), 0, st, (int)tw_cnt, wb, ws, gp, twg);
-    ZK_CHECK(hipGetLastError());
+  }
+  // fused radix-2 GLV stages; the inverse's first stage takes twn and dkn
+  uint32_t *run_glv() {
+    uint64_t *twn = glv_twiddles(true), *dkn = twg + 2 * tw_cnt * 8;
     const unsigned grid = (unsigned)(glanes / 256);
     uint32_t *in = A, *out = B;
     int k0 = 0;
-    if (inverse) {  // first stage with N^-1 folded in: twn = (w^-1)^j N^-1, dkn = N^-1 (decomposed)
-      zkh::Fe<HR> nn = one;
-      for (int k = 0; k < m; k++) zkh::add(nn, nn, nn);
-      zkh::inv(ninv, nn);
-      for (int j = 0; j < 4; j++) wn.w[j] = ninv.v[j];
-      uint64_t *twn = twg + tw_cnt * 8, *dkn = twg + 2 * tw_cnt * 8;
-      hipLaunchKernelGGL(k_fft_tw_glv<Fr>, dim3(div_up(tw_cnt, 256)), dim3(256), 0, st, (int)tw_cnt, wb, wn, gp, twn);
-      ZK_CHECK(hipGetLastError());
-      hipLaunchKernelGGL(k_fft_tw_glv<Fr>, dim3(1), dim3(256), 0, st, 1, wb, wn, gp, dkn);
-      ZK_CHECK(hipGetLastError());
+    if (inverse) {
       hipLaunchKernelGGL(k_fft_inv_first_glv<C>, dim3(grid), dim3(256), 0, st, m, in, out, twn, dkn, beta, scratch,
                          (int)glanes);
       ZK_CHECK(hipGetLastError());
       std::swap(in, out);
       k0 = 1;
     }
+    const auto stage = inverse ? k_fft_inv_stage_glv<C> : k_fft_fwd_stage_glv<C>;
     for (int k = k0; k < m; k++) {
-      const int s = inverse ? m - k : k + 1;
-      if (inverse)
-        hipLaunchKernelGGL(k_fft_inv_stage_glv<C>, dim3(grid), dim3(256), 0, st, m, s, in, out, twg, beta, scratch,
-                           (int)glanes);
-      else
-        hipLaunchKernelGGL(k_fft_fwd_stage_glv<C>, dim3(grid), dim3(256), 0, st, m, s, in, out, twg, beta, scratch,
-                           (int)glanes);
+      hipLaunchKernelGGL(stage, dim3(grid), dim3(256), 0, st, m, inverse ? m - k : k + 1, in, out, twg, beta, scratch,
+                         (int)glanes);
       ZK_CHECK(hipGetLastError());
       std::swap(in, out);
     }
     return in;
-  };
-  auto run_int = [&] {
+  }
+  // the reference's exact integer schedule
+  uint32_t *run_int() {
     int_twiddles_t<C>(st, gen, inverse, tw_cnt, tw);
-    const unsigned grid = (unsigned)(lanes / 256);
+    const auto stage = inverse ? k_fft_inv_stage<C> : k_fft_fwd_stage<C>;
     uint32_t *in = A, *out = B;
     for (int k = 0; k < m; k++) {
-      const int s = inverse ? m - k : k + 1;
-      if (inverse)
-        hipLaunchKernelGGL(k_fft_inv_stage<C>, dim3(grid), dim3(256), 0, st, m, s, in, out, tw, scratch, (int)lanes);
-      else
-        hipLaunchKernelGGL(k_fft_fwd_stage<C>, dim3(grid), dim3(256), 0, st, m, s, in, out, tw, scratch, (int)lanes);
+      hipLaunchKernelGGL(stage, dim3((unsigned)(lanes / 256)), dim3(256), 0, st, m, inverse ? m - k : k + 1, in, out, tw,
+                         scratch, (int)lanes);
       ZK_CHECK(hipGetLastError());
       std::swap(in, out);
     }
     return in;
+  }
+};
+
+template <class C>
+static void g1_fft_t(Device &dev, int m, const uint64_t *gen, const uint64_t *src, uint64_t *tgt, bool host_io,
+                     bool inverse, bool jac) {
+  using F = typename C::Fp;
+  using HF = typename HostOf<C>::Fp;
+  constexpr int NP = C::NP64;
+  ZK_REQUIRE(m >= 0 && m <= 26, "G1 fft: log2 size out of range (0..26)");
+  hipStream_t st = dev.stream;
+  G1Fft<C> f(st, m, gen, inverse);
+  const size_t N = f.N, tw_cnt = f.tw_cnt;
+  const bool radix = !f.rbits.empty();
+  const size_t tlanes = std::max(std::max(f.lanes, f.glanes), f.rlanes);
+  const size_t nbad = div_up(N, 256);
+  dev.arena.reserve(N * 3 * NP * 8 * (host_io ? 2 : 0) + 3 * N * xw<F>() * 4 + tlanes * scl_tab_words<F>() * 4 +
+                    tw_cnt * 32 + 2 * tw_cnt * 64 + 64 + nbad * 4 + N * NP * 8 + f.pbuf * xw<F>() * 4 + (1 << 20));
+  dev.arena.reset();
+  StagedIO io(dev, host_io, src, N * 3 * NP, tgt, N * 3 * NP);
+  f.A = dev.arena.take<uint32_t>(N * xw<F>());
+  f.B = dev.arena.take<uint32_t>(N * xw<F>());
+  f.scratch = dev.arena.take<uint32_t>(tlanes * scl_tab_words<F>());
+  f.tw = dev.arena.take<uint64_t>(tw_cnt * 4);
+  f.twg = dev.arena.take<uint64_t>(2 * tw_cnt * 8 + 8);
+  uint32_t *bad = dev.arena.take<uint32_t>(nbad);
+  uint64_t *nscratch = dev.arena.take<uint64_t>(N * NP);
+  f.Pb = radix ? dev.arena.take<uint32_t>(f.pbuf * xw<F>()) : nullptr;
+
+  // input order: bit-reversed for the radix-2 forward stages, natural for the inverse (DIF) and the
+  // Stockham radix-2^b stages
+  auto load_points = [&](bool natural) {
+    with_flag(jac, [&](auto J) {
+      hipLaunchKernelGGL((k_fft_load<C, decltype(J)::value>), dim3(div_up(N, 256)), dim3(256), 0, st, (int)N,
+                         (inverse || natural) ? 0 : m, io.in, f.A);
+    });
+    ZK_CHECK(hipGetLastError());
   };
+  // GLV stages when every point is in the order-r subgroup (always on BN254, cofactor 1; checked on
+  // BLS12-381).  ZK_FFT_GLV=0: the integer stages always (A/B hook, read once).
+  static const bool glv_on = env_on("ZK_FFT_GLV");
+  const bool use_radix = radix && glv_on;
+  load_points(use_radix);
+  bool glv = glv_on && m > 0;
+  SubgroupTest test;
+  if (glv && C::NP64 == 6) test.launch<C>(dev, N, f.glanes, f.A, f.beta, bad);
+  uint32_t *res = f.A;
   bool out_natural = false;
   if (glv) {
-    uint32_t *res = use_radix ? run_radix() : run_glv();
-    if (hb) {  // the speculative membership test's verdict
-      const hipEvent_t checked = dev.split_event(1);
-      for (;;) {
-        const hipError_t e = hipEventQuery(checked);
-        if (e == hipSuccess) break;
-        if (e != hipErrorNotReady) ZK_CHECK(e);
-        std::this_thread::yield();
-      }
-      for (unsigned i = 0; i < cgrid; i++) glv = glv && hb[i] == 0;
-    }
+    res = use_radix ? f.run_radix() : f.run_glv();
+    glv = test.passed(dev);
     if (glv) {
-      A = res;
       out_natural = use_radix;
-    } else {  // some point lies outside the r-subgroup: the reference's exact integer schedule
+    } else {  // some point lies outside the r-subgroup: discard the GLV result, rerun from the input
       ZK_CHECK(hipStreamSynchronize(st));
       load_points(false);
-      A = run_int();
+      res = f.run_int();
     }
   } else if (m > 0) {
-    A = run_int();
+    res = f.run_int();
   }
   g1_fft_last_glv().store(glv ? 1 : 0);
-  const int chk = norm_chk(N);
-  launch_norm<C, MODE_XYZZ_TO_PROJ>(st, (int)N, chk, A, nscratch, dt, exp_p_minus_2<HF>(),
+  launch_norm<C, MODE_XYZZ_TO_PROJ>(st, (int)N, norm_chk(N), res, nscratch, io.out, exp_p_minus_2<HF>(),
                                     (inverse && !out_natural) ? m : 0);
-  ZK_CHECK(hipGetLastError());
-  if (host_io) copy_to_host(dev, st, tgt, dt, N * 3 * NP * 8);  // fresh caller arrays: zk_runtime.hpp
-  ZK_CHECK(hipStreamSynchronize(st));
+  io.finish();
 }
 
 // ---------------------------------------------------------------------------- public
 
 void g1_batch_from_affine(int curve, int n, const uint64_t *src, uint64_t *tgt, bool host_io, bool jac) {
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  if (curve == 0) batch_from_affine_t<BN254>(dev, n, src, tgt, host_io, jac);
-  else batch_from_affine_t<BLS381>(dev, n, src, tgt, host_io, jac);
+  with_g1(curve, [&](Device &dev, auto c) { batch_from_affine_t<decltype(c)>(dev, n, src, tgt, host_io, jac); });
 }
 void g1_batch_to_affine(int curve, int n, const uint64_t *src, uint64_t *tgt, bool host_io, bool jac) {
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  if (curve == 0) batch_to_affine_t<BN254>(dev, n, src, tgt, host_io, jac);
-  else batch_to_affine_t<BLS381>(dev, n, src, tgt, host_io, jac);
+  with_g1(curve, [&](Device &dev, auto c) { batch_to_affine_t<decltype(c)>(dev, n, src, tgt, host_io, jac); });
 }
 int g1_fft_plan(int curve, int m, int *bits, int cap) {
   if (m <= 0) return 0;
-  const std::vector<int> v = radix_plan(m, curve == 0 ? fft_waves<BN254>() : fft_waves<BLS381>());
+  const std::vector<int> v = radix_plan(m, on_curve<BN254, BLS381>(curve, [](auto c) { return fft_waves<decltype(c)>(); }));
   for (int i = 0; i < (int)v.size() && i < cap; i++) bits[i] = v[i];
   return (int)v.size();
 }
 int g1_fft_radix_products(int b) { return b >= 1 && b <= 4 ? radix_products(b) : 0; }
 void g1_fft(int curve, int m, const uint64_t *gen, const uint64_t *src, uint64_t *tgt, bool host_io, bool inverse,
             bool jac) {
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  if (curve == 0) g1_fft_t<BN254>(dev, m, gen, src, tgt, host_io, inverse, jac);
-  else g1_fft_t<BLS381>(dev, m, gen, src, tgt, host_io, inverse, jac);
+  with_g1(curve, [&](Device &dev, auto c) { g1_fft_t<decltype(c)>(dev, m, gen, src, tgt, host_io, inverse, jac); });
 }
 
 }  // namespace zk

@@ -10,14 +10,17 @@
 // zk_g1ext.hip): per lane a strided chunk of prefix products, one safegcd inversion, the walk back.
 // Two kernels, because Fp2 coordinates do not fit beside the inversion (the G1 kernel already sits
 // at 248-254 VGPRs on BLS12-381):
-//   k_g2_norm_chain  reads only Z, leaves 1/N(Z_i) (Fp, internal form) in scratch
+//   k_g2_norm_chain  reads only Z, leaves 1/N(Z_i) (Fp, internal form) in scratch; the chain itself
+//                    (g2_norm_chain_body, zk_g2norm.hpp) is shared with the G2 transform's normalisation
 //   k_g2_apply       one thread per point: X conj(Z) / N(Z), Y conj(Z) / N(Z), canonical
 // Rows with Z = 0 (whatever X and Y hold) take the factor 1 in the chain and come out as the
 // all-0xFF affine sentinel, like the reference.
 #include "zk_curve.hpp"
+#include "zk_dispatch.hpp"
 #include "zk_extdev.hpp"
 #include "zk_g1ext.hpp"
 #include "zk_g2ext.hpp"
+#include "zk_g2norm.hpp"
 #include "zk_host.hpp"
 #include "zk_msm.hpp"
 #include "zk_runtime.hpp"
@@ -54,51 +57,13 @@ __device__ __forceinline__ bool g2_load_z(Fe<B> &z0, Fe<B> &z1, const uint64_t *
   return !(fe_is_zero(z0) && fe_is_zero(z1));
 }
 
-// The chunk of lane t is the strided set {t, t + T, ...} (T = lanes), CHK rows at most; every step is
-// branch-free (rows with Z = 0 take the factor 1) and every load and store unconditional, as in
-// k_norm_chunks.  ninv[i] holds the running product on the way up and 1 / N(Z_i) on the way back.
+// the shared chain (zk_g2norm.hpp) on the projective rows' Z
 template <class C>
 __global__ void __launch_bounds__(256) k_g2_norm_chain(int n, int CHK, const uint64_t *__restrict__ src,
                                                        uint64_t *__restrict__ ninv, int lanes) {
   using B = typename C::Fp::Base;
-  constexpr int NP = C::NP64, NB = NP / 2;
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t T = (size_t)lanes;
-  if (t >= T || t >= (size_t)n) return;
-  const size_t left = ((size_t)n - t + T - 1) / T;
-  const size_t cnt = left < (size_t)CHK ? left : (size_t)CHK;
-  Fe<B> P, one_int;
-  fe_one(P);
-  fe_one(one_int);
-  auto norm = [&](size_t i, Fe<B> &f) {  // z0^2 + z1^2 (one shared reduction), or 1 where Z = 0
-    Fe<B> z0, z1, nn;
-    const bool fin = g2_load_z<B, NP>(z0, z1, src, i);
-    fe_mul2(nn, z0, z0, z1, z1);
-#pragma unroll
-    for (int l = 0; l < B::N; l++) f.v[l] = fin ? nn.v[l] : one_int.v[l];
-  };
-  for (size_t k = 0; k < cnt; k++) {
-    const size_t i = t + k * T;
-    Fe<B> f, q;
-    norm(i, f);
-    fe_mul(q, P, f);
-    P = q;
-    fe_store_ref(ninv + i * NB, P);  // running product (internal form, packed)
-  }
-  Fe<B> inv;
-  fe_inv_sg(inv, P);
-  for (size_t kk = cnt; kk-- > 0;) {
-    const size_t i = t + kk * T;
-    Fe<B> f, e, prev, dinv, q;
-    norm(i, f);
-    fe_load_ref(e, ninv + (kk > 0 ? i - T : i) * NB);
-#pragma unroll
-    for (int l = 0; l < B::N; l++) prev.v[l] = kk > 0 ? e.v[l] : one_int.v[l];
-    fe_mul(dinv, inv, prev);  // 1 / N(Z_i)
-    fe_mul(q, inv, f);
-    inv = q;
-    fe_store_ref(ninv + i * NB, dinv);
-  }
+  g2_norm_chain_body<C>(n, CHK, ninv, lanes,
+                        [&](size_t i, Fe<B> &z0, Fe<B> &z1) { return g2_load_z<B, C::NP64>(z0, z1, src, i); });
 }
 
 template <class C>
@@ -109,14 +74,11 @@ __global__ void __launch_bounds__(256) k_g2_apply(int n, const uint64_t *__restr
   constexpr int NP = C::NP64, NB = NP / 2;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)n) return;
-  Fe<B> z0, z1, ni, c0, c1, m;
+  Fe<B> z0, z1, ni;
   const bool fin = g2_load_z<B, NP>(z0, z1, src, i);
-  fe_load_ref(ni, ninv + i * NB);
-  fe_mul(c0, z0, ni);  // 1 / Z = conj(Z) / N(Z)
-  fe_mul(m, z1, ni);
-  fe_neg(c1, m);
   Fe<F> zi, X, Y, x, y;
-  f2_join(zi, c0, c1);
+  fe_load_ref(ni, ninv + i * NB);
+  g2_inv_from_norm(zi, z0, z1, ni);
   ld_int(X, src + i * 3 * NP);
   ld_int(Y, src + i * 3 * NP + NP);
   fe_mul(x, X, zi);
@@ -152,18 +114,11 @@ static void g2_batch_from_affine_t(Device &dev, int n, const uint64_t *src, uint
   const size_t N = (size_t)n;
   dev.arena.reserve(N * 5 * NP * 8 + (1 << 20));
   dev.arena.reset();
-  const uint64_t *ds = src;
-  uint64_t *dt = tgt;
-  if (host_io) {
-    uint64_t *a = dev.arena.take<uint64_t>(N * 2 * NP);
-    ZK_CHECK(hipMemcpyAsync(a, src, N * 2 * NP * 8, hipMemcpyHostToDevice, st));
-    ds = a;
-    dt = dev.arena.take<uint64_t>(N * 3 * NP);
-  }
-  hipLaunchKernelGGL(k_g2_from_affine<C>, dim3(div_up(N, 256)), dim3(256), 0, st, n, ds, dt, one_ref_base<HB>());
+  StagedIO io(dev, host_io, src, N * 2 * NP, tgt, N * 3 * NP);
+  hipLaunchKernelGGL(k_g2_from_affine<C>, dim3(div_up(N, 256)), dim3(256), 0, st, n, io.in, io.out,
+                     one_ref_base<HB>());
   ZK_CHECK(hipGetLastError());
-  if (host_io) copy_to_host(dev, st, tgt, dt, N * 3 * NP * 8);  // fresh caller arrays: zk_runtime.hpp
-  ZK_CHECK(hipStreamSynchronize(st));
+  io.finish();
 }
 
 template <class C>
@@ -174,38 +129,25 @@ static void g2_batch_to_affine_t(Device &dev, int n, const uint64_t *src, uint64
   const size_t N = (size_t)n;
   dev.arena.reserve(N * 6 * NP * 8 + (1 << 20));
   dev.arena.reset();
-  const uint64_t *ds = src;
-  uint64_t *dt = tgt;
-  if (host_io) {
-    uint64_t *a = dev.arena.take<uint64_t>(N * 3 * NP);
-    ZK_CHECK(hipMemcpyAsync(a, src, N * 3 * NP * 8, hipMemcpyHostToDevice, st));
-    ds = a;
-    dt = dev.arena.take<uint64_t>(N * 2 * NP);
-  }
+  StagedIO io(dev, host_io, src, N * 3 * NP, tgt, N * 2 * NP);
   uint64_t *ninv = dev.arena.take<uint64_t>(N * NB);
   const int chk = norm_chk(N);  // points per inversion, as the G1 conversion
   const size_t lanes = (N + chk - 1) / chk;
-  hipLaunchKernelGGL(k_g2_norm_chain<C>, dim3(div_up(lanes, 256)), dim3(256), 0, st, n, chk, ds, ninv, (int)lanes);
+  hipLaunchKernelGGL(k_g2_norm_chain<C>, dim3(div_up(lanes, 256)), dim3(256), 0, st, n, chk, io.in, ninv,
+                     (int)lanes);
   ZK_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_g2_apply<C>, dim3(div_up(N, 256)), dim3(256), 0, st, n, ds, ninv, dt);
+  hipLaunchKernelGGL(k_g2_apply<C>, dim3(div_up(N, 256)), dim3(256), 0, st, n, io.in, ninv, io.out);
   ZK_CHECK(hipGetLastError());
-  if (host_io) copy_to_host(dev, st, tgt, dt, N * 2 * NP * 8);
-  ZK_CHECK(hipStreamSynchronize(st));
+  io.finish();
 }
 
 // ---------------------------------------------------------------------------- public
 
 void g2_batch_from_affine(int curve, int n, const uint64_t *src, uint64_t *tgt, bool host_io) {
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  if (curve == 0) g2_batch_from_affine_t<BN254_G2>(dev, n, src, tgt, host_io);
-  else g2_batch_from_affine_t<BLS381_G2>(dev, n, src, tgt, host_io);
+  with_g2(curve, [&](Device &dev, auto c) { g2_batch_from_affine_t<decltype(c)>(dev, n, src, tgt, host_io); });
 }
 void g2_batch_to_affine(int curve, int n, const uint64_t *src, uint64_t *tgt, bool host_io) {
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  if (curve == 0) g2_batch_to_affine_t<BN254_G2>(dev, n, src, tgt, host_io);
-  else g2_batch_to_affine_t<BLS381_G2>(dev, n, src, tgt, host_io);
+  with_g2(curve, [&](Device &dev, auto c) { g2_batch_to_affine_t<decltype(c)>(dev, n, src, tgt, host_io); });
 }
 
 }  // namespace zk

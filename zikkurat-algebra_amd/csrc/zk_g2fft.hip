@@ -23,16 +23,19 @@
 // Normalisation (x = X / ZZ, y = Y / ZZZ as (x : y : 1), infinity (0 : 1 : 0), canonical limbs, the
 // reference's normalize, G2_proj.c:70-89) inverts ZZZ over Fp2 by the norm trick of zk_g2ext.hip:
 // 1 / ZZZ = conj(ZZZ) / N(ZZZ), N = z0^2 + z1^2 in the base field, the norms sharing inversions by
-// Montgomery's trick; then x = X (ZZ / ZZZ)^2, y = Y / ZZZ.  Chain and apply are separate kernels for
-// the reason given in zk_g2ext.hip.  An input row with Z = 0 is the point at infinity.
+// Montgomery's trick (the chain and the inverse-from-norm step are zk_g2norm.hpp's, shared with that
+// unit); then x = X (ZZ / ZZZ)^2, y = Y / ZZZ.  Chain and apply are separate kernels for the reason given
+// in zk_g2ext.hip.  An input row with Z = 0 is the point at infinity.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
 #include "zk_curve.hpp"
+#include "zk_dispatch.hpp"
 #include "zk_extdev.hpp"
 #include "zk_fftdev.hpp"
 #include "zk_g1ext.hpp"
 #include "zk_g2ext.hpp"
+#include "zk_g2norm.hpp"
 #include "zk_host.hpp"
 #include "zk_msm.hpp"
 #include "zk_runtime.hpp"
@@ -183,51 +186,15 @@ __device__ __forceinline__ bool g2_load_zzz(Fe<typename F::Base> &z0, Fe<typenam
   return !(fe_is_zero(z0) && fe_is_zero(z1));
 }
 
-// k_g2_norm_chain (zk_g2ext.hip) on the XYZZ rows' ZZZ: lane t walks the strided chunk {t, t + T, ...},
-// CHK rows at most, branch-free (infinity takes the factor 1); ninv[i] = 1 / N(ZZZ_i) on return
+// the shared chain (g2_norm_chain_body, zk_g2norm.hpp) on the XYZZ rows' ZZZ: ninv[i] = 1 / N(ZZZ_i) on
+// return, infinity taking the factor 1
 template <class C>
 __global__ void __launch_bounds__(256) k_g2_fft_norm_chain(int n, int CHK, const uint32_t *__restrict__ A,
                                                            uint64_t *__restrict__ ninv, int lanes) {
   using F = typename C::Fp;
   using B = typename F::Base;
-  constexpr int NB = C::NP64 / 2;
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t T = (size_t)lanes;
-  if (t >= T || t >= (size_t)n) return;
-  const size_t left = ((size_t)n - t + T - 1) / T;
-  const size_t cnt = left < (size_t)CHK ? left : (size_t)CHK;
-  Fe<B> P, one_int;
-  fe_one(P);
-  fe_one(one_int);
-  auto norm = [&](size_t i, Fe<B> &f) {  // z0^2 + z1^2 (one shared reduction), or 1 at infinity
-    Fe<B> z0, z1, nn;
-    const bool fin = g2_load_zzz<F>(z0, z1, A, i);
-    fe_mul2(nn, z0, z0, z1, z1);
-#pragma unroll
-    for (int l = 0; l < B::N; l++) f.v[l] = fin ? nn.v[l] : one_int.v[l];
-  };
-  for (size_t k = 0; k < cnt; k++) {
-    const size_t i = t + k * T;
-    Fe<B> f, q;
-    norm(i, f);
-    fe_mul(q, P, f);
-    P = q;
-    fe_store_ref(ninv + i * NB, P);  // running product (internal form, packed)
-  }
-  Fe<B> inv;
-  fe_inv_sg(inv, P);
-  for (size_t kk = cnt; kk-- > 0;) {
-    const size_t i = t + kk * T;
-    Fe<B> f, e, prev, dinv, q;
-    norm(i, f);
-    fe_load_ref(e, ninv + (kk > 0 ? i - T : i) * NB);
-#pragma unroll
-    for (int l = 0; l < B::N; l++) prev.v[l] = kk > 0 ? e.v[l] : one_int.v[l];
-    fe_mul(dinv, inv, prev);  // 1 / N(ZZZ_i)
-    fe_mul(q, inv, f);
-    inv = q;
-    fe_store_ref(ninv + i * NB, dinv);
-  }
+  g2_norm_chain_body<C>(n, CHK, ninv, lanes,
+                        [&](size_t i, Fe<B> &z0, Fe<B> &z1) { return g2_load_zzz<F>(z0, z1, A, i); });
 }
 
 // one thread per point: 1 / ZZZ = conj(ZZZ) / N(ZZZ), 1 / Z = ZZ / ZZZ, x = X / Z^2, y = Y / ZZZ, written
@@ -241,16 +208,13 @@ __global__ void __launch_bounds__(256) k_g2_fft_norm_apply(int n, int bitrev_m, 
   constexpr int NP = C::NP64, NB = NP / 2;  // u64 words per Fp2 / Fp element
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)n) return;
-  Fe<B> z0, z1, ni, c0, c1, mm;
+  Fe<B> z0, z1, ni;
   const bool fin = g2_load_zzz<F>(z0, z1, A, i);
+  Fe<F> izzz, iz, iz2, x, y;
   fe_load_ref(ni, ninv + i * NB);
-  fe_mul(c0, z0, ni);
-  fe_mul(mm, z1, ni);
-  fe_neg(c1, mm);
+  g2_inv_from_norm(izzz, z0, z1, ni);
   Xyzz<F> p;
   xyzz_load(p, A + i * xw<F>());
-  Fe<F> izzz, iz, iz2, x, y;
-  f2_join(izzz, c0, c1);
   fe_mul(iz, p.ZZ, izzz);  // ZZ / ZZZ = 1 / Z
   fe_sqr(iz2, iz);
   fe_mul(x, p.X, iz2);
@@ -304,14 +268,7 @@ static void g2_fft_t(Device &dev, int m, const uint64_t *gen, const uint64_t *sr
   dev.arena.reserve((host_io ? 2 : 0) * N * 3 * NP * 8 + 2 * N * xw<F>() * 4 + lanes * scl_tab_words<F>() * 4 +
                     tw_cnt * 32 + N * NB * 8 + (1 << 20));
   dev.arena.reset();
-  const uint64_t *ds = src;
-  uint64_t *dt = tgt;
-  if (host_io) {
-    uint64_t *a = dev.arena.take<uint64_t>(N * 3 * NP);
-    ZK_CHECK(hipMemcpyAsync(a, src, N * 3 * NP * 8, hipMemcpyHostToDevice, st));
-    ds = a;
-    dt = dev.arena.take<uint64_t>(N * 3 * NP);
-  }
+  StagedIO io(dev, host_io, src, N * 3 * NP, tgt, N * 3 * NP);
   uint32_t *A = dev.arena.take<uint32_t>(N * xw<F>());
   uint32_t *Bf = dev.arena.take<uint32_t>(N * xw<F>());
   uint32_t *scratch = dev.arena.take<uint32_t>(lanes * scl_tab_words<F>());
@@ -319,10 +276,11 @@ static void g2_fft_t(Device &dev, int m, const uint64_t *gen, const uint64_t *sr
   uint64_t *ninv = dev.arena.take<uint64_t>(N * NB);
 
   // input order: bit-reversed for the forward (DIT) stages, natural for the inverse (DIF)
-  hipLaunchKernelGGL((k_fft_load<C, false>), dim3(div_up(N, 256)), dim3(256), 0, st, (int)N, inverse ? 0 : m, ds, A);
+  hipLaunchKernelGGL((k_fft_load<C, false>), dim3(div_up(N, 256)), dim3(256), 0, st, (int)N, inverse ? 0 : m, io.in,
+                     A);
   ZK_CHECK(hipGetLastError());
   if (m > 0) {
-    fft_int_twiddles(NB == 4 ? 0 : 1, st, gen, inverse, tw_cnt, tw);
+    fft_int_twiddles(C::ID, st, gen, inverse, tw_cnt, tw);
     const dim3 sgrid((unsigned)(lanes / 256)), bgrid(div_up(N, 256));
     for (int k = 0; k < m; k++) {
       const int s = inverse ? m - k : k + 1;
@@ -345,20 +303,16 @@ static void g2_fft_t(Device &dev, int m, const uint64_t *gen, const uint64_t *sr
                      (int)nlanes);
   ZK_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_g2_fft_norm_apply<C>, dim3(div_up(N, 256)), dim3(256), 0, st, (int)N, inverse ? m : 0, A, ninv,
-                     dt);
+                     io.out);
   ZK_CHECK(hipGetLastError());
-  if (host_io) copy_to_host(dev, st, tgt, dt, N * 3 * NP * 8);  // fresh caller arrays: zk_runtime.hpp
-  ZK_CHECK(hipStreamSynchronize(st));
+  io.finish();
 }
 
 // ---------------------------------------------------------------------------- public
 
 void g2_fft(int curve, int m, const uint64_t *gen, const uint64_t *src, uint64_t *tgt, bool host_io, bool inverse) {
   ZK_REQUIRE(m >= 0 && m <= G2_FFT_MAX_LOG, "G2 fft: log2 size out of range (0..24)");
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  if (curve == 0) g2_fft_t<BN254_G2>(dev, m, gen, src, tgt, host_io, inverse);
-  else g2_fft_t<BLS381_G2>(dev, m, gen, src, tgt, host_io, inverse);
+  with_g2(curve, [&](Device &dev, auto c) { g2_fft_t<decltype(c)>(dev, m, gen, src, tgt, host_io, inverse); });
 }
 void g2_fft_set_max_lanes(int lanes) {
   g2_fft_max_lanes.store(lanes > 0 ? (((size_t)lanes + 255) & ~(size_t)255) : G2_FFT_LANES);

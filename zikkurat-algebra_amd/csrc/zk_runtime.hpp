@@ -224,4 +224,48 @@ void timer_read_all(double *total_ms, long *launches);
 
 inline unsigned div_up(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
+// Readers of the ZK_* A/B switches.  A call site keeps the result in a `static const` of its own, so
+// every switch is read once per process, at first use.
+inline bool env_on(const char *name) {  // default on: false only for a value starting with '0'
+  const char *e = getenv(name);
+  return !(e && e[0] == '0');
+}
+inline bool env_is1(const char *name) {  // default off: true only for a value starting with '1'
+  const char *e = getenv(name);
+  return e && e[0] == '1';
+}
+inline long env_pos(const char *name, long dflt) {  // the positive integer value, else dflt
+  const char *e = getenv(name);
+  const long v = e ? atol(e) : 0;
+  return v > 0 ? v : dflt;
+}
+inline int env_int(const char *name, int dflt) {  // atoi of any set value (0 and below included), else dflt
+  const char *e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+// Device-side input and output of an entry point that also takes host arrays (caller holds dev.mu;
+// construct after the call's arena.reserve / reset).  host_io: both buffers come from the arena and
+// the input's upload is enqueued on dev.stream; otherwise `in` / `out` are the caller's device
+// pointers.  finish() copies the result back (host_io) and waits for the stream.
+struct StagedIO {
+  Device &dev;
+  const uint64_t *in;
+  uint64_t *out;
+  uint64_t *host_out;  // the caller's host array, or null
+  size_t out_words;
+  StagedIO(Device &d, bool host_io, const uint64_t *src, size_t in_words, uint64_t *tgt, size_t out_words_)
+      : dev(d), in(src), out(tgt), host_out(host_io ? tgt : nullptr), out_words(out_words_) {
+    if (!host_io) return;
+    uint64_t *a = dev.arena.take<uint64_t>(in_words);
+    ZK_CHECK(hipMemcpyAsync(a, src, in_words * 8, hipMemcpyHostToDevice, dev.stream));
+    in = a;
+    out = dev.arena.take<uint64_t>(out_words);
+  }
+  void finish() {
+    if (host_out) copy_to_host(dev, dev.stream, host_out, out, out_words * 8);  // fresh caller arrays: above
+    ZK_CHECK(hipStreamSynchronize(dev.stream));
+  }
+};
+
 }  // namespace zk
