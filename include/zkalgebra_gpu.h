@@ -444,6 +444,11 @@ ZKG_API void zkg_ntt_set_table_max(size_t entries);
 /* test hook: blocks per launch of the batched pass kernel of zkg_ntt_ext* (a pass with more tiles
  * runs as several launches; default and maximum 2^21, 0 restores it) */
 ZKG_API void zkg_ntt_ext_set_max_grid(unsigned tiles);
+/* test hook: device bytes of cached NTT twiddle sets one context keeps; building a set that would
+ * exceed it first frees the least recently used ones (default 8 GiB; 0 restores it) */
+ZKG_API void zkg_ntt_set_cache_limit(size_t bytes);
+/* device bytes of the NTT twiddle sets and coset shift tables cached for the calling thread's device */
+ZKG_API size_t zkg_ntt_cache_bytes(void);
 /* test hook: device bytes one working-set arena may hold (0: unlimited), to exercise the
  * out-of-memory degrade path (smaller MSM window groups) */
 ZKG_API void zkg_arena_set_limit(size_t bytes);

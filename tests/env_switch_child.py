@@ -89,6 +89,8 @@ def _to_affine(job, A, out):
 def _fft(job, A, out):
     c, m = job["curve"], job["m"]
     sg = zk.get_fft_subgroup(c, m)
+    if "gen" in job:  # another generator of the same subgroup
+        sg = zk.FFTSubgroup(c, tuple(int(v) for v in A[job["gen"]]), m)
     f = zk.inverse_fft if job["inverse"] else zk.forward_fft
     out[job["id"]] = f(sg, A[job["pts"]], coords=job["coords"])
     out[job["id"] + "__glv"] = np.array([zk.g1_fft_last_glv()])

@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 
 import field_edges as fe
+import generators
 import golden_io
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -252,8 +253,12 @@ def forced_plan(radix, m):
     return plan
 
 
-def _fft_case(ctx, bt, curve, coords, m, pts, tag, glv, plan):
+def _fft_case(ctx, bt, curve, coords, m, pts, tag, glv, plan, root=None):
     gen = ctx.gpu.get_fft_subgroup(curve, m).gen_array()
+    extra = {}
+    if root is not None:  # a named root of tests/generators.py instead of the canonical generator
+        gen = generators.root(curve, m, gen, root)
+        extra["gen"] = bt.put(tag + "_gen", gen)
     kin = bt.put(tag + "_in", pts)
     for inverse in (False, True):
         name = f"G1_{coords}_fft_{'inverse' if inverse else 'forward'}"
@@ -263,7 +268,7 @@ def _fft_case(ctx, bt, curve, coords, m, pts, tag, glv, plan):
             ctx.reference.arr(curve, name, m, gen, pts, w)
             return w
         jid = bt.job(id=f"{tag}_{'inv' if inverse else 'fwd'}", call="fft", curve=curve, coords=coords, m=m,
-                     inverse=inverse, pts=kin)
+                     inverse=inverse, pts=kin, **extra)
         bt.expect(jid, cached(("fft_want", tag, inverse), want))
         bt.expect(jid + "__glv", [glv])
         if plan is not None:
@@ -286,6 +291,14 @@ def fft(ctx, bt, sizes=FFT_SIZES, radix=None, glv=1, nonsubgroup=False):
         aff = golden_io.bls_nonsubgroup_points(1 << m, 300 + m)
         pts = cached(("nonsub", m), lambda: ctx.gpu.batch_from_affine(curve, aff))
         _fft_case(ctx, bt, curve, "proj", m, pts, f"fftns_{curve}_{m}", 0, None)
+
+
+def fft_other_generator(ctx, bt, radix, m=5, root="cube"):
+    """the forced stages with a generator other than the canonical one (tests/generators.py), projective,
+    one size per curve: the stage twiddles are derived from the generator argument"""
+    for curve in CURVES:
+        pts = _points(ctx, curve, "proj", 1 << m, 200 + m, 2)
+        _fft_case(ctx, bt, curve, "proj", m, pts, f"fftgen_{curve}_{m}_{root}", 1, forced_plan(radix, m), root=root)
 
 
 def fft_norm(ctx, bt):
@@ -651,7 +664,8 @@ def _rows():
     # group FFT: the fused radix-2 stages, radix 4 / 8 / 16 Stockham stages with remainder stages,
     # and the integer stages
     for radix in (1, 2, 3, 4):
-        add({"ZK_FFT_RADIX": str(radix)}, lambda ctx, bt, r=radix: fft(ctx, bt, radix=r))
+        add({"ZK_FFT_RADIX": str(radix)}, lambda ctx, bt, r=radix: fft(ctx, bt, radix=r),
+            *([lambda ctx, bt: fft_other_generator(ctx, bt, 1)] if radix == 1 else []))
     add({"ZK_FFT_GLV": "0"}, lambda ctx, bt: fft(ctx, bt, glv=0, nonsubgroup=True))
     # G1 MSM, bit jobs.  ZK_MSM_BITS_G=1 asks for one block, msm_bits_groups caps the chunk at
     # BITACC_MAX_K = 256 and msm_run_bits spreads the pairs evenly over the blocks that leaves:

@@ -41,10 +41,11 @@ def ref_inv(ref, curve, s):
     return out
 
 
-def expected_one(ref, zk, curve, m, x, inverse, shift):
-    """one transform of 2^m rows"""
+def expected_one(ref, zk, curve, m, x, inverse, shift, gen=None):
+    """one transform of 2^m rows (gen: the subgroup generator, the canonical one when not given)"""
     n = 1 << m
-    gen = zk.get_fft_subgroup(curve, m).gen_array()
+    if gen is None:
+        gen = zk.get_fft_subgroup(curve, m).gen_array()
     x = np.ascontiguousarray(x)
     if shift is None:
         return ref.ntt(curve, m, gen, x, inverse)
@@ -53,9 +54,9 @@ def expected_one(ref, zk, curve, m, x, inverse, shift):
     return ref_mul(ref, curve, ref.ntt(curve, m, gen, x, True), ref_powers(ref, zk, curve, n, ref_inv(ref, curve, shift)))
 
 
-def expected(ref, zk, curve, m, x, inverse, shift, batch):
+def expected(ref, zk, curve, m, x, inverse, shift, batch, gen=None):
     n = 1 << m
-    return np.concatenate([expected_one(ref, zk, curve, m, x[b * n:(b + 1) * n], inverse, shift)
+    return np.concatenate([expected_one(ref, zk, curve, m, x[b * n:(b + 1) * n], inverse, shift, gen)
                            for b in range(batch)]) if batch else x[:0]
 
 
@@ -81,8 +82,9 @@ def shifts(zk, curve, m):
             "subgroup": zk.get_fft_subgroup(curve, m + 1).gen_array()}
 
 
-def run_device(zk, curve, m, x, inverse, shift, batch, inplace=False):
-    gen = zk.get_fft_subgroup(curve, m).gen_array()
+def run_device(zk, curve, m, x, inverse, shift, batch, inplace=False, gen=None):
+    if gen is None:
+        gen = zk.get_fft_subgroup(curve, m).gen_array()
     d_src = zk.DeviceBuffer(x)
     d_dst = d_src if inplace else zk.DeviceBuffer.empty(x.nbytes)
     try:

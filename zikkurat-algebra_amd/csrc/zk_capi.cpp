@@ -321,6 +321,8 @@ ZKG_API void zkg_ntt_set_max_radix(int r) { zk::ntt_set_max_radix(r); }
 
 ZKG_API void zkg_ntt_set_table_max(size_t entries) { zk::ntt_set_table_max(entries); }
 ZKG_API void zkg_ntt_ext_set_max_grid(unsigned tiles) { zk::ntt_ext_set_max_grid(tiles); }
+ZKG_API void zkg_ntt_set_cache_limit(size_t bytes) { zk::ntt_set_cache_limit(bytes); }
+ZKG_API size_t zkg_ntt_cache_bytes(void) { return guard_ret<size_t>(0, [&] { return zk::ntt_cache_bytes(); }); }
 ZKG_API void zkg_arena_set_limit(size_t bytes) { zk::arena_set_limit(bytes); }
 ZKG_API int zkg_msm_last_groups(void) { return zk::msm_last_groups_read(); }
 ZKG_API size_t zkg_msm_workspace_bytes(int curve, int npoints, int expo_nlimbs, int expos_mont, int host_inputs,

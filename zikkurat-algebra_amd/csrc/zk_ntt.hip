@@ -530,6 +530,12 @@ static std::map<TwKey, TwSet> g_tw;  // entries of context d are only touched un
 static std::mutex g_tw_mu;          // guards the map structure itself
 static uint64_t g_tw_clock = 0;
 static const size_t TW_CACHE_LIMIT = (size_t)8 << 30;
+static std::atomic<size_t> g_tw_cache_limit{0};  // test hook (ntt_set_cache_limit); 0 = the default
+void ntt_set_cache_limit(size_t bytes) { g_tw_cache_limit.store(bytes); }
+static size_t tw_cache_limit() {
+  const size_t v = g_tw_cache_limit.load();
+  return v ? v : TW_CACHE_LIMIT;
+}
 
 // The per-context walk of a cache map (g_tw, g_sh: the first key field is context uid * 2 + curve), under g_tw_mu:
 // fn(it) for every entry of the context; fn may erase it
@@ -617,10 +623,11 @@ static TwSet &twiddles(Device &dev, int m, const uint64_t *gen_mont, bool invers
   }
   // evict least-recently used sets of this context beyond the cache limit (and, when the
   // device is out of memory, until the new set fits)
+  const size_t limit = tw_cache_limit();
   for (;;) {
     size_t total = words * 8;
     for_context(g_tw, dev, [&](auto it2) { total += it2->second.bytes; });
-    if (total <= TW_CACHE_LIMIT || !evict_lru(g_tw, dev)) break;
+    if (total <= limit || !evict_lru(g_tw, dev)) break;
   }
   TwSet ts;
   ts.bytes = words * 8;
@@ -897,6 +904,7 @@ struct ShSet {
   uint64_t *mem = nullptr;
   uint64_t *slo = nullptr, *shi = nullptr;
   int h = 0;
+  size_t bytes = 0;
   uint64_t last_use = 0;
 };
 // (context uid * 2 + curve, m, inverse | scaled << 1, shift)
@@ -933,7 +941,8 @@ static const ShSet &shift_table(Device &dev, int m, const uint64_t *shift_mont, 
   }
   ShSet ss;
   const size_t words = (((size_t)1 << h) + ((size_t)1 << (m - h))) * el + pows.size();
-  while (hipMalloc(&ss.mem, words * 8) != hipSuccess) {
+  ss.bytes = words * 8;
+  while (hipMalloc(&ss.mem, ss.bytes) != hipSuccess) {
     (void)hipGetLastError();
     ZK_REQUIRE(evict_lru(g_sh, dev), "ntt: out of device memory for the shift table");
   }
@@ -1048,6 +1057,15 @@ void ntt_release(Device &dev) {
   std::lock_guard<std::mutex> lock(g_tw_mu);
   drop_entries(g_tw, dev);
   drop_entries(g_sh, dev);
+}
+
+size_t ntt_cache_bytes() {
+  Device &dev = current_device();
+  std::lock_guard<std::mutex> lock(g_tw_mu);
+  size_t total = 0;
+  for_context(g_tw, dev, [&](auto it) { total += it->second.bytes; });
+  for_context(g_sh, dev, [&](auto it) { total += it->second.bytes; });
+  return total;
 }
 
 void ntt(int curve, int m, const uint64_t *gen_mont, const uint64_t *src, uint64_t *dst, bool host_io,

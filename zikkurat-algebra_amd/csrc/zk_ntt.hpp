@@ -24,6 +24,11 @@ void ntt_set_max_radix(int r);
 // test hook: entries above which a pass computes its inter-pass twiddles on the fly instead of
 // reading a cached table (default 2^25; 0 restores it)
 void ntt_set_table_max(size_t entries);
+// test hook: bytes of cached twiddle sets one context keeps before it evicts the least recently used
+// (default 8 GiB; 0 restores it)
+void ntt_set_cache_limit(size_t bytes);
+// bytes of the twiddle sets and coset shift tables cached for the calling thread's device
+size_t ntt_cache_bytes();
 struct Device;
 // one transform between DEVICE buffers, enqueued on dev.stream without touching the arena and
 // without waiting (caller holds dev.mu): d_src -> d_dst through `scratch`, three distinct buffers

@@ -79,6 +79,8 @@ EXTENSION_SYMBOLS += ["zkg_poly_mul_device", "zkg_poly_eval_device", "zkg_poly_l
 POLY_MUL_MAX_LOG = {"bn128": 28, "bls12_381": 30}   # largest product, log2 of n1 + n2 - 1
 # coset and batched NTT
 EXTENSION_SYMBOLS += ["zkg_ntt_ext_device", "zkg_ntt_ext", "zkg_ntt_ext_set_max_grid"]
+# cache hooks of the NTT twiddle and shift tables
+EXTENSION_SYMBOLS += ["zkg_ntt_set_cache_limit", "zkg_ntt_cache_bytes"]
 
 _lib = None
 
@@ -120,6 +122,10 @@ def load():
         lib.zkg_timer_read.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_long)]
         lib.zkg_msm_set_group_limit.argtypes = [ctypes.c_size_t]
         lib.zkg_ntt_set_table_max.argtypes = [ctypes.c_size_t]
+        if hasattr(lib, "zkg_ntt_set_cache_limit"):  # as above: absent from an older variant build
+            lib.zkg_ntt_set_cache_limit.argtypes = [ctypes.c_size_t]
+            lib.zkg_ntt_cache_bytes.restype = ctypes.c_size_t
+            lib.zkg_ntt_cache_bytes.argtypes = []
         lib.zkg_arena_set_limit.argtypes = [ctypes.c_size_t]
         lib.zkg_msm_workspace_bytes.restype = ctypes.c_size_t
         lib.zkg_msm_workspace_bytes.argtypes = [ctypes.c_int] * 7
@@ -947,6 +953,16 @@ def ntt_ext_set_max_grid(tiles):
 def ntt_set_table_max(entries):
     """test hook: inter-pass twiddle entries above which NTT passes compute twiddles on the fly (0: default)"""
     load().zkg_ntt_set_table_max(int(entries))
+
+
+def ntt_set_cache_limit(nbytes):
+    """test hook: bytes of cached twiddle sets one context keeps before evicting (0: the default, 8 GiB)"""
+    load().zkg_ntt_set_cache_limit(int(nbytes))
+
+
+def ntt_cache_bytes():
+    """device bytes of the twiddle sets and coset shift tables cached for the calling thread's device"""
+    return int(load().zkg_ntt_cache_bytes())
 
 
 def arena_set_limit(nbytes):
