@@ -242,8 +242,11 @@ ZKG_API uint8_t bls12_381_poly_mont_quot_by_vanishing( int n1, const uint64_t *s
  * mul_naive is what Haskell's (*) and sqr on Poly call (Poly.hs:133); it computes the same
  * coefficients by a direct kernel (short factor) or by NTTs, so n1 + n2 - 1 is limited to 2^28
  * (bn128) / 2^30 (bls12_381): beyond it the call fails through the error channel.  src1 == src2
- * is allowed; tgt aliases no input of mul_naive, lincomb and eval_at.  get_coeff, is_constant,
- * long_div, quot and rem are NOT provided. */
+ * is allowed; tgt aliases no input of mul_naive, lincomb and eval_at.  long_div, quot and rem are
+ * provided in Part 2 as zkg_poly_long_div / zkg_poly_long_div_device (the curve as first argument,
+ * then the reference's argument list; quot and rem are that call with a NULL output), not under
+ * the reference's names: the reference's symbols stay the reference's own CPU definitions until a
+ * separate change exports aliases.  get_coeff and is_constant are NOT provided. */
 ZKG_API int     bn128_poly_mont_degree   ( int n1, const uint64_t *src1 );
 ZKG_API uint8_t bn128_poly_mont_is_zero  ( int n1, const uint64_t *src1 );
 ZKG_API uint8_t bn128_poly_mont_is_equal ( int n1, const uint64_t *src1, int n2, const uint64_t *src2 );
@@ -383,6 +386,37 @@ ZKG_API void zkg_poly_lincomb_device(int curve, int K, const int *ns, const uint
  * else log2 of the transform size) */
 ZKG_API void zkg_poly_set_mul_direct_max(int len);
 ZKG_API int zkg_poly_last_mul_path(void);
+
+/* Division with remainder: src1 = quot * src2 + rem, deg rem < deg src2 -- the contract of
+ * <C>_poly_mont_long_div (bls12_381_poly_mont.c:249-297), every output word bit-identical to it for
+ * canonical Montgomery inputs; computed by Newton inversion of the reversed divisor over the NTT.
+ * With dp, dq the degrees (-1: zero polynomial or length 0): quot[0, dp - dq] and rem[0, dq) are
+ * written and the rest of the nquot / nrem rows is zero; the divisor need not be monic; dq < 0
+ * zeroes both outputs; dp < dq gives quotient 0 and rem[0, dp] = src1.  quot and / or rem may be
+ * NULL (<C>_poly_mont_rem / _quot) and are then never touched.  Outputs alias no input and not each
+ * other.  Returns 0, or -1 with nothing written (a return code; the error channel stays clear) for
+ * a negative length, quot with nquot < dp - dq + 1, rem with nrem < dq (nrem < dp + 1 when
+ * dp < dq), or n1 > 2^27 (bn128) / 2^29 (bls12_381) -- the last on the length alone, before a
+ * pointer is read.  A workspace that does not fit goes through the error channel.  Synchronous and
+ * thread-safe, on the calling thread's device. */
+ZKG_API int zkg_poly_long_div_device(int curve, int n1, const uint64_t *d_src1, int n2, const uint64_t *d_src2,
+                                     int nquot, uint64_t *d_quot, int nrem, uint64_t *d_rem);   /* DEVICE pointers */
+ZKG_API int zkg_poly_long_div(int curve, int n1, const uint64_t *src1, int n2, const uint64_t *src2,
+                              int nquot, uint64_t *quot, int nrem, uint64_t *rem);               /* HOST pointers */
+/* test hooks: terms of the series inverse's base kernel (< 0: the default; 0, 1: one term; larger
+ * values are clamped to the kernel's capacity) and the value in force; the precision plan for a
+ * quotient of m coefficients (returns the Newton steps s, the smallest with base * 2^s >= m, and
+ * writes prec[0] = base kernel terms, prec[1..s] = precision after each step, prec[s] = m, at most
+ * cap entries; -1 for m <= 0; no GPU call); the Newton steps of the most recent division (-1: it
+ * took an early exit: zero divisor, dp < dq, refused) */
+ZKG_API void zkg_poly_set_div_base_max(int len);
+ZKG_API int  zkg_poly_div_base_max(void);
+ZKG_API int  zkg_poly_div_plan(int m, int *prec, int cap);
+ZKG_API int  zkg_poly_last_div_steps(void);
+/* timing hook: while on, a division records events around its phases; ms[0..2] = series inverse,
+ * quotient, remainder of the most recent profiled division */
+ZKG_API void zkg_poly_div_profile(int on);
+ZKG_API void zkg_poly_last_div_phase_ms(double *ms);
 
 
 /* device-resident G1 group FFT / batch_to_affine (d_* DEVICE pointers, gen on the host) */

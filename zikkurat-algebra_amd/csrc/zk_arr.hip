@@ -1117,6 +1117,14 @@ void arr_mul_enqueue(Device &dev, int curve, size_t n, const uint64_t *d_a, cons
   if (curve == 0) launch_arr_op<BN_Fr>(ARR_MUL, g, dim3(stream_grid(n, true)), dev.stream);
   else launch_arr_op<BLS_Fr>(ARR_MUL, g, dim3(stream_grid(n, true)), dev.stream);
 }
+void poly_degree_enqueue(Device &dev, int n, const uint64_t *d_a, int *d_deg) {
+  ZK_CHECK(hipMemsetAsync(d_deg, 0xff, 4, dev.stream));  // -1
+  if (n <= 0) return;
+  const size_t N = (size_t)n;
+  hipLaunchKernelGGL(k_degree, dim3((unsigned)std::min<size_t>(DEG_GRID, (N + DEG_CHUNK - 1) / DEG_CHUNK)), dim3(256), 0,
+                     dev.stream, n, d_a, d_deg);
+  ZK_CHECK(hipGetLastError());
+}
 int poly_degree(int curve, int n, const uint64_t *a, bool host_io) {
   Device &dev = current_device();
   std::lock_guard<std::mutex> lock(dev.mu);

@@ -49,5 +49,9 @@ struct Device;
 // d_tgt = d_a * d_b element-wise on DEVICE buffers, enqueued on dev.stream without touching the
 // arena and without waiting (caller holds dev.mu; n < 2^31): the pointwise step of zk_poly.hip
 void arr_mul_enqueue(Device &dev, int curve, size_t n, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_tgt);
+// *d_deg = degree of the DEVICE array d_a[0, n) (-1: zero or n <= 0), the reduction of poly_degree
+// enqueued on dev.stream without touching the arena and without waiting (caller holds dev.mu): the
+// division of zk_poly.hip finds both of its degrees with one wait
+void poly_degree_enqueue(Device &dev, int n, const uint64_t *d_a, int *d_deg);
 
 }  // namespace zk

@@ -240,6 +240,21 @@ ZKG_API void zkg_poly_lincomb_device(int curve, int K, const int *ns, const uint
                                      const uint64_t *const *d_polys, uint64_t *d_tgt) {
   guard([&] { zk::poly_lincomb(curve, K, ns, coeffs, d_polys, d_tgt, false); });
 }
+// <C>_poly_mont_{long_div,quot,rem} (bls12_381_poly_mont.c:249-309) with the curve as first argument
+ZKG_API int zkg_poly_long_div_device(int curve, int n1, const uint64_t *d_src1, int n2, const uint64_t *d_src2,
+                                     int nquot, uint64_t *d_quot, int nrem, uint64_t *d_rem) {
+  return guard_ret(-1, [&] { return zk::poly_long_div(curve, n1, d_src1, n2, d_src2, nquot, d_quot, nrem, d_rem, false); });
+}
+ZKG_API int zkg_poly_long_div(int curve, int n1, const uint64_t *src1, int n2, const uint64_t *src2, int nquot,
+                              uint64_t *quot, int nrem, uint64_t *rem) {
+  return guard_ret(-1, [&] { return zk::poly_long_div(curve, n1, src1, n2, src2, nquot, quot, nrem, rem, true); });
+}
+ZKG_API void zkg_poly_set_div_base_max(int len) { zk::poly_set_div_base_max(len); }
+ZKG_API int zkg_poly_div_base_max(void) { return zk::poly_div_base_max(); }
+ZKG_API int zkg_poly_div_plan(int m, int *prec, int cap) { return zk::poly_div_plan(m, prec, cap); }
+ZKG_API int zkg_poly_last_div_steps(void) { return zk::poly_last_div_steps(); }
+ZKG_API void zkg_poly_div_profile(int on) { zk::poly_div_profile(on); }
+ZKG_API void zkg_poly_last_div_phase_ms(double *ms) { zk::poly_last_div_phase_ms(ms); }
 ZKG_API void zkg_poly_set_mul_direct_max(int len) { zk::poly_set_mul_direct_max(len); }
 ZKG_API int zkg_poly_last_mul_path(void) { return zk::poly_last_mul_path(); }
 

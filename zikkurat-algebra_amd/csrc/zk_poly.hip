@@ -5,6 +5,8 @@
 //       (what Haskell's (*) and sqr on Poly bind to: Poly.hs:133 "mul = mulNaive")
 //   <C>_poly_mont_eval_at     bls12_381_poly_mont.c:225-243   (serial Horner loop)
 //   <C>_poly_mont_lincomb     bls12_381_poly_mont.c:169-195
+//   <C>_poly_mont_long_div / _quot / _rem   bls12_381_poly_mont.c:249-309   (as zkg_poly_long_div:
+//       Newton inversion of the reversed divisor over the NTT, "division" below)
 // Every coefficient of every result is an exact canonical field element, so the output is
 // bit-identical to the reference's loops whatever algorithm computes it.
 //
@@ -316,6 +318,210 @@ __global__ void __launch_bounds__(256) k_poly_lincomb(int K, int N, const LcRow 
   if (i < N) st(tgt, (size_t)i, acc);
 }
 
+// ---------------------------------------------------------------------------- division
+
+// Series inverse, base case: g = f^-1 mod x^k for k <= DIV_BASE_CAP, where f_j = d[dq - j] for
+// j < kf and 0 above (f = rev(d), f_0 the divisor's leading coefficient, nonzero).  One wavefront:
+//   g_0 = f_0^-1,   g_i = -g_0 sum_{j = 1..i} f_j g_{i-j}.
+// f (converted once to the internal radix, < 2p) and g (reference form, canonical) sit in LDS; lane
+// t takes the LAZY_J products j = 1 + LAZY_J t ... of term i under one reduction (the bound of
+// k_poly_mul_direct: x = g canonical, s = f < 2p), the lanes' sums are added across the wavefront,
+// and lane 0 closes the term: (g_0 R')(S R) / R' = g_0 S R.
+constexpr int DIV_BASE_CAP = 256;
+static_assert(64 * LAZY_J >= DIV_BASE_CAP, "one wavefront covers every j of the last term");
+template <class F>
+__global__ void __launch_bounds__(64) k_div_inv_base(int k, int kf, int dq, const uint64_t *__restrict__ d,
+                                                     uint64_t *__restrict__ g) {
+  __shared__ uint32_t sf[DIV_BASE_CAP * F::N];
+  __shared__ uint32_t sg[DIV_BASE_CAP * F::N];
+  const int lane = threadIdx.x;
+  for (int j = lane; j < k; j += 64) {
+    Fe<F> v, vi;
+    fe_zero(vi);
+    if (j < kf) {
+      ld(v, d, (size_t)(dq - j));
+      fe_to_int(vi, v);
+    }
+    lds_put(sf + j * F::N, vi);
+  }
+  __syncthreads();
+  Fe<F> g0i;  // f_0^-1 R'
+  {
+    Fe<F> f0;
+    lds_get(f0, sf);
+    fe_inv_sg(g0i, f0);
+  }
+  if (lane == 0) {
+    Fe<F> g0;
+    fe_to_ref(g0, g0i);
+    lds_put(sg, g0);
+  }
+  __syncthreads();
+  for (int i = 1; i < k; i++) {
+    uint64_t T[2 * F::N - 1];
+#pragma unroll
+    for (int q = 0; q < 2 * F::N - 1; q++) T[q] = 0;
+    const int j0 = 1 + lane * LAZY_J;
+#pragma unroll
+    for (int u = 0; u < LAZY_J; u++) {
+      const int j = j0 + u;
+      if (j <= i) {
+        Fe<F> x, c;
+        lds_get(x, sg + (i - j) * F::N);
+        lds_get(c, sf + j * F::N);
+        cols_add(T, x, c);
+      }
+    }
+    Fe<F> r, t;
+    redc_cols(r, T);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      Fe<F> other;
+#pragma unroll
+      for (int q = 0; q < F::N; q++) other.v[q] = __shfl_down(r.v[q], o, 64);
+      fe_add(t, r, other);
+      r = t;
+    }
+    if (lane == 0) {
+      Fe<F> gi, ng;
+      fe_mul(gi, g0i, r);
+      fe_neg(ng, gi);
+      fe_canon(ng);
+      lds_put(sg + i * F::N, ng);
+    }
+    __syncthreads();
+  }
+  for (int i = lane; i < k; i += 64) {
+    Fe<F> x;
+    lds_get(x, sg + i * F::N);
+    st(g, (size_t)i, x);
+  }
+}
+
+// Both operands of a Newton step or of the quotient's product into their zero-padded transform
+// buffers in ONE launch, 16 B per lane: x[j] = a[atop - j] for j < na (the reversal: rows walked
+// down from the leading coefficient), y[j] = b[j] for j < nb, zero up to N.
+__global__ void __launch_bounds__(256) k_div_rev_pad2(size_t N, size_t na, const uint64_t *__restrict__ a, size_t atop,
+                                                      uint64_t *__restrict__ x, size_t nb,
+                                                      const uint64_t *__restrict__ b, uint64_t *__restrict__ y) {
+  const size_t per = N * 2;  // 16-B chunks per buffer
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const uint4 z = make_uint4(0, 0, 0, 0);
+  const uint4 *ua = reinterpret_cast<const uint4 *>(a), *ub = reinterpret_cast<const uint4 *>(b);
+  uint4 *ux = reinterpret_cast<uint4 *>(x), *uy = reinterpret_cast<uint4 *>(y);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * per; i += stride) {
+    if (i < per) {
+      const size_t row = i >> 1;
+      ux[i] = row < na ? ua[(atop - row) * 2 + (i & 1)] : z;
+    } else {
+      const size_t c = i - per;
+      uy[c] = c < nb * 2 ? ub[c] : z;
+    }
+  }
+}
+// The second operand of a Newton step: y[j] = -w[k + j] for j < cnt (the coefficients k .. k' - 1 of
+// f g, negated here so that the step's last product is the correction itself), zero up to N
+template <class F>
+__global__ void __launch_bounds__(256) k_div_neg_shift_pad(size_t N, const uint64_t *__restrict__ w, size_t k, size_t cnt,
+                                                           uint64_t *__restrict__ y) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < N; j += stride) {
+    Fe<F> v, nv;
+    fe_zero(nv);
+    if (j < cnt) {
+      ld(v, w, k + j);
+      fe_neg(nv, v);
+    }
+    st(y, j, nv);
+  }
+}
+// quot[i] = w[m - 1 - i], i < m: the truncation of the reversed quotient's product to m
+// coefficients, written back in natural order
+__global__ void __launch_bounds__(256) k_div_rev_trunc(size_t m, const uint64_t *__restrict__ w,
+                                                       uint64_t *__restrict__ quot) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const uint4 *uw = reinterpret_cast<const uint4 *>(w);
+  uint4 *uq = reinterpret_cast<uint4 *>(quot);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * m; i += stride)
+    uq[i] = uw[(m - 1 - (i >> 1)) * 2 + (i & 1)];
+}
+// The quotient on the direct kernel's terms (m <= POLY_MUL_DIRECT_MAX): rev(q) = rev(p) g mod x^m is
+//   quot[i] = sum_{j = 0..m-1-i} g[j] p[dq + i + j],   i < m,
+// one lane per coefficient i, g in LDS tiles in the internal radix, the accumulation of
+// k_poly_mul_direct.  The largest row read is p[dq + m - 1] = p[dp].
+template <class F>
+__global__ void __launch_bounds__(256) k_div_quot_direct(int m, int dq, const uint64_t *__restrict__ p,
+                                                         const uint64_t *__restrict__ g, uint64_t *__restrict__ quot) {
+  __shared__ uint32_t sh[PM_TILE * F::N];
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  Fe<F> acc;
+  fe_zero(acc);
+  for (int j0 = 0; j0 < m; j0 += PM_TILE) {
+    const int cnt = min(PM_TILE, m - j0);
+    __syncthreads();  // the previous tile has been read
+    if ((int)threadIdx.x < cnt) {
+      Fe<F> v, vi;
+      ld(v, g, (size_t)(j0 + threadIdx.x));
+      fe_to_int(vi, v);
+      lds_put(sh + threadIdx.x * F::N, vi);
+    }
+    __syncthreads();
+    for (int jj = 0; jj < cnt; jj += LAZY_J) {  // block-uniform trip counts
+      const int mq = min(LAZY_J, cnt - jj);
+      uint64_t T[2 * F::N - 1];
+#pragma unroll
+      for (int q = 0; q < 2 * F::N - 1; q++) T[q] = 0;
+#pragma unroll
+      for (int u = 0; u < LAZY_J; u++) {
+        if (u < mq) {
+          const long long j = j0 + jj + u;
+          const bool in = i < m && i + j < m;
+          Fe<F> x, c;
+          ld(x, p, (size_t)(in ? dq + i + j : 0));  // row 0 exists; its product is masked out
+          if (!in) fe_zero(x);
+          lds_get(c, sh + (jj + u) * F::N);
+          cols_add(T, x, c);
+        }
+      }
+      Fe<F> r, t;
+      redc_cols(r, T);
+      fe_add(t, acc, r);
+      acc = t;
+    }
+  }
+  if (i < m) st(quot, (size_t)i, acc);
+}
+// dst[j] = sum over t of src[j + t N], j < N (rows at or above len count as zero): the image of
+// src mod x^N - 1.  One lane per j; the host folds by at most DIV_FOLD_MAX terms per pass.
+constexpr int DIV_FOLD_MAX = 64;
+template <class F>
+__global__ void __launch_bounds__(256) k_div_fold(size_t len, const uint64_t *__restrict__ src, size_t N,
+                                                  uint64_t *__restrict__ dst) {
+  const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= N) return;
+  Fe<F> acc, x, t;
+  fe_zero(acc);
+  for (size_t i = j; i < len; i += N) {
+    ld(x, src, i);
+    fe_add(t, acc, x);
+    acc = t;
+  }
+  st(dst, j, acc);
+}
+// rem[j] = a[j] - w[j], j < n: fold(p) minus the cyclic product fold(q) fold(d), truncated to deg d
+template <class F>
+__global__ void __launch_bounds__(256) k_div_rem(size_t n, const uint64_t *__restrict__ a, const uint64_t *__restrict__ w,
+                                                 uint64_t *__restrict__ rem) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
+    Fe<F> x, y, r;
+    ld(x, a, j);
+    ld(y, w, j);
+    fe_sub(r, x, y);
+    st(rem, j, r);
+  }
+}
+
 // ---------------------------------------------------------------------------- host side
 
 struct CfgBN { using Fd = BN_Fr; using Fh = zkh::BN_Fr; };
@@ -505,6 +711,243 @@ void poly_lincomb_t(Device &dev, int K, const int *ns, const uint64_t *coeffs, c
   ZK_CHECK(hipStreamSynchronize(s));
 }
 
+// ---------------------------------------------------------------------------- division, host side
+//
+// p = q d + r with deg r < deg d, by Newton inversion of the reversed divisor (m = dp - dq + 1):
+//   g = rev(d)^-1 mod x^m,   rev(q) = rev(p) g mod x^m,   r = p - q d mod x^dq.
+// Series inverse: the base kernel gives prec[0] terms, every Newton step takes k to k' <= 2k terms
+// with transforms of length N = 2^ceil(log2 k') only: the cyclic product c = f_{<k'} g_{<k} mod
+// x^N - 1 wraps k + k' - 1 - N <= k coefficients onto places whose true value is known (f g = 1 mod
+// x^k), so c[k, k') are the coefficients h of f g there, and g[k, k') = -(g_{<k} h) mod x^(k'-k),
+// a product of k' - 1 <= N coefficients that does not wrap.  Five transforms of length N a step.
+// Quotient: one product of 2m - 1 coefficients (three transforms), or the direct kernel.
+// Remainder: one cyclic product of length 2^ceil(log2 dq) on the folded operands (three transforms).
+
+// Base kernel terms by default: 16.  Measured (profiles/poly_div_base_sweep.txt: whole division at
+// m = 2^8, 2^12, 2^16 against base sizes 1 .. 256, both curves): 16 is the fastest at all three
+// sizes (0.540 / 1.137 / 1.940 ms on bn128), 8 and 32 within 3 % of it, 256 up to twice as slow --
+// a base term costs one serial pass through the wavefront, a Newton step about a dozen launches.
+constexpr int DIV_BASE_DEFAULT = 16;
+std::atomic<int> g_div_base{-1};
+std::atomic<int> g_last_div_steps{-1};
+std::atomic<int> g_div_profile{0};
+std::mutex g_div_phase_mu;
+double g_div_phase_ms[3] = {0, 0, 0};
+
+int div_base_in_force() {
+  const int v = g_div_base.load();
+  if (v < 0) return DIV_BASE_DEFAULT;
+  return v <= 1 ? 1 : std::min(v, DIV_BASE_CAP);
+}
+// precisions of the series inverse: prec[0] from the base kernel, prec[i] after step i; s is the
+// smallest count with base 2^s >= m and prec[i] = ceil(m / 2^(s - i)), so every step at most
+// doubles and the last one ends at exactly m
+int div_plan(int m, int base, int *prec, int cap) {
+  if (m <= 0) return -1;
+  int s = 0;
+  while (((long long)base << s) < m) s++;
+  for (int i = 0; i <= s && i < cap; i++) prec[i] = (int)(((long long)m + ((1ll << (s - i)) - 1)) >> (s - i));
+  return s;
+}
+int host_degree(int n, const uint64_t *a) {
+  for (long long i = (long long)n - 1; i >= 0; i--)
+    if (a[4 * i] | a[4 * i + 1] | a[4 * i + 2] | a[4 * i + 3]) return (int)i;
+  return -1;
+}
+unsigned copy_grid(size_t items) { return (unsigned)std::min<size_t>((items + 255) / 256, 8192); }
+
+struct DivBufs {
+  uint64_t *x, *y, *fx, *fg, *z, *scratch;
+};
+// fx = NTT(x), fg = NTT(y), x = the cyclic product of length 2^lg of what x and y held
+void div_cyclic_product(Device &dev, int curve, int lg, const DivBufs &b) {
+  uint64_t gen[4];
+  zkg_fft_generator(curve, lg, gen);
+  ntt_enqueue(dev, curve, lg, gen, b.x, b.fx, b.scratch, false);
+  ntt_enqueue(dev, curve, lg, gen, b.y, b.fg, b.scratch, false);
+  arr_mul_enqueue(dev, curve, (size_t)1 << lg, b.fx, b.fg, b.z);
+  ntt_enqueue(dev, curve, lg, gen, b.z, b.x, b.scratch, true);
+}
+// rows of the first fold pass of a source of len rows down to N (0: one pass is enough)
+size_t fold_first(size_t len, size_t N) {
+  if (len <= (size_t)DIV_FOLD_MAX * N) return 0;
+  return ((size_t)1 << ceil_log2(len)) / DIV_FOLD_MAX;  // a power of two above N
+}
+// dst[0, N) = src[0, len) mod x^N - 1, through t0 / t1 when one lane would add more than DIV_FOLD_MAX rows
+template <class F>
+void div_fold(hipStream_t s, const uint64_t *src, size_t len, size_t N, uint64_t *dst, uint64_t *t0, uint64_t *t1) {
+  for (size_t Np = fold_first(len, N); Np; Np = fold_first(len, N)) {
+    hipLaunchKernelGGL(k_div_fold<F>, dim3(div_up(Np, 256)), dim3(256), 0, s, len, src, Np, t0);
+    ZK_CHECK(hipGetLastError());
+    src = t0;
+    len = Np;
+    std::swap(t0, t1);
+  }
+  hipLaunchKernelGGL(k_div_fold<F>, dim3(div_up(N, 256)), dim3(256), 0, s, len, src, N, dst);
+  ZK_CHECK(hipGetLastError());
+}
+
+template <class Cfg>
+int poly_div_t(Device &dev, int curve, int n1, const uint64_t *p, int n2, const uint64_t *d, int nquot, uint64_t *quot,
+               int nrem, uint64_t *rem, bool host_io) {
+  using F = typename Cfg::Fd;
+  hipStream_t s = dev.stream;
+  g_last_div_steps.store(-1);
+  // degrees: the device reduction for device operands (one wait for both); host operands are read
+  // from the top where they lie, so that only the rows up to the degree are staged, once
+  int dp, dq;
+  if (host_io) {
+    dp = host_degree(n1, p);
+    dq = host_degree(n2, d);
+  } else {
+    dev.arena.reserve(1 << 20);
+    dev.arena.reset();
+    int *ddeg = dev.arena.take<int>(2);
+    poly_degree_enqueue(dev, n1, p, ddeg);
+    poly_degree_enqueue(dev, n2, d, ddeg + 1);
+    int *hdeg = reinterpret_cast<int *>(dev.host_staging(8));
+    ZK_CHECK(hipMemcpyAsync(hdeg, ddeg, 8, hipMemcpyDeviceToHost, s));
+    ZK_CHECK(hipStreamSynchronize(s));
+    dp = hdeg[0];
+    dq = hdeg[1];
+  }
+  // what the reference asserts (poly_mont.c:252-253, 267)
+  if (quot && (long long)nquot < (long long)dp - dq + 1) return -1;
+  if (rem && dq >= 0 && nrem < (dp < dq ? dp + 1 : dq)) return -1;
+  auto zero_rows = [&](uint64_t *t, size_t from, size_t to) {
+    if (!t || to <= from) return;
+    if (host_io) memset(t + from * 4, 0, (to - from) * 32);
+    else ZK_CHECK(hipMemsetAsync(t + from * 4, 0, (to - from) * 32, s));
+  };
+  if (dq < 0 || dp < dq) {  // division by zero: all zero; dp < dq: quotient 0, remainder p (poly_mont.c:255-271)
+    zero_rows(quot, 0, (size_t)nquot);
+    const size_t keep = dq < 0 ? 0 : (size_t)(dp + 1);
+    if (rem && keep) {
+      if (host_io) memcpy(rem, p, keep * 32);
+      else ZK_CHECK(hipMemcpyAsync(rem, p, keep * 32, hipMemcpyDeviceToDevice, s));
+    }
+    zero_rows(rem, keep, (size_t)nrem);
+    if (!host_io) ZK_CHECK(hipStreamSynchronize(s));
+    return 0;
+  }
+  const int m = dp - dq + 1, kf = std::min(m, dq + 1);  // only kf coefficients of d reach the quotient
+  int prec[40];
+  const int steps = div_plan(m, div_base_in_force(), prec, 40);
+  const int dm = g_direct_max.load();
+  const bool direct_q = m <= (dm < 0 ? POLY_MUL_DIRECT_MAX : dm);
+  const bool want_rem = rem && dq >= 1;
+  const int lgq = std::max(ceil_log2((size_t)2 * m - 1), POLY_MUL_MIN_LOG);
+  const int lgr = want_rem ? std::max(ceil_log2((size_t)dq), POLY_MUL_MIN_LOG) : 0;
+  // working set, reserved once: six transform buffers of the largest length any phase needs, g, the
+  // quotient where the caller's is not a device buffer, and the staged operands and remainder
+  size_t NB = 0;
+  for (int i = 1; i <= steps; i++) NB = std::max(NB, (size_t)1 << std::max(ceil_log2((size_t)prec[i]), POLY_MUL_MIN_LOG));
+  if (!direct_q) NB = std::max(NB, (size_t)1 << lgq);
+  if (want_rem) NB = std::max({NB, (size_t)1 << lgr, fold_first((size_t)dp + 1, (size_t)1 << lgr)});
+  const bool own_q = host_io || !quot;
+  const size_t M = (size_t)m;
+  dev.arena.reserve((6 * NB + M + (own_q ? M : 0) +
+                     (host_io ? (size_t)dp + 1 + (size_t)dq + 1 + (want_rem ? (size_t)dq : 0) : 0)) * 32 + (1 << 20));
+  dev.arena.reset();
+  const uint64_t *dpl = p, *ddv = d;
+  if (host_io) {
+    uint64_t *a = dev.arena.take<uint64_t>(((size_t)dp + 1) * 4), *b = dev.arena.take<uint64_t>(((size_t)dq + 1) * 4);
+    ZK_CHECK(hipMemcpyAsync(a, p, ((size_t)dp + 1) * 32, hipMemcpyHostToDevice, s));
+    ZK_CHECK(hipMemcpyAsync(b, d, ((size_t)dq + 1) * 32, hipMemcpyHostToDevice, s));
+    dpl = a;
+    ddv = b;
+  }
+  DivBufs B;
+  B.x = dev.arena.take<uint64_t>(NB * 4);
+  B.y = dev.arena.take<uint64_t>(NB * 4);
+  B.fx = dev.arena.take<uint64_t>(NB * 4);
+  B.fg = dev.arena.take<uint64_t>(NB * 4);
+  B.z = dev.arena.take<uint64_t>(NB * 4);
+  B.scratch = dev.arena.take<uint64_t>(NB * 4);
+  uint64_t *g = dev.arena.take<uint64_t>(M * 4);
+  uint64_t *dqo = own_q ? dev.arena.take<uint64_t>(M * 4) : quot;
+  uint64_t *dro = !want_rem ? nullptr : host_io ? dev.arena.take<uint64_t>((size_t)dq * 4) : rem;
+
+  const bool prof = g_div_profile.load() != 0;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  auto mark = [&](int i) {
+    if (!prof) return;
+    ZK_CHECK(hipEventCreate(&ev[i]));
+    ZK_CHECK(hipEventRecord(ev[i], s));
+  };
+  mark(0);
+  // ---- series inverse
+  int k = prec[0];
+  hipLaunchKernelGGL(k_div_inv_base<F>, dim3(1), dim3(64), 0, s, k, std::min(k, kf), dq, ddv, g);
+  ZK_CHECK(hipGetLastError());
+  for (int i = 1; i <= steps; i++) {
+    const int kn = prec[i], lg = std::max(ceil_log2((size_t)kn), POLY_MUL_MIN_LOG);
+    const size_t N = (size_t)1 << lg;
+    hipLaunchKernelGGL(k_div_rev_pad2, dim3(copy_grid(4 * N)), dim3(256), 0, s, N, (size_t)std::min(kn, kf), ddv,
+                       (size_t)dq, B.x, (size_t)k, g, B.y);
+    ZK_CHECK(hipGetLastError());
+    div_cyclic_product(dev, curve, lg, B);  // x = f_{<k'} g_{<k} mod x^N - 1, fg = NTT(g_{<k})
+    hipLaunchKernelGGL(k_div_neg_shift_pad<F>, dim3(copy_grid(N)), dim3(256), 0, s, N, B.x, (size_t)k,
+                       (size_t)(kn - k), B.y);
+    ZK_CHECK(hipGetLastError());
+    uint64_t gen[4];
+    zkg_fft_generator(curve, lg, gen);
+    ntt_enqueue(dev, curve, lg, gen, B.y, B.fx, B.scratch, false);
+    arr_mul_enqueue(dev, curve, N, B.fx, B.fg, B.z);
+    ntt_enqueue(dev, curve, lg, gen, B.z, B.x, B.scratch, true);  // x[0, k' - k) = g[k, k')
+    ZK_CHECK(hipMemcpyAsync(g + (size_t)k * 4, B.x, (size_t)(kn - k) * 32, hipMemcpyDeviceToDevice, s));
+    k = kn;
+  }
+  mark(1);
+  // ---- quotient
+  if (direct_q) {
+    hipLaunchKernelGGL(k_div_quot_direct<F>, dim3(div_up(M, 256)), dim3(256), 0, s, m, dq, dpl, g, dqo);
+    ZK_CHECK(hipGetLastError());
+  } else {
+    const size_t N = (size_t)1 << lgq;
+    hipLaunchKernelGGL(k_div_rev_pad2, dim3(copy_grid(4 * N)), dim3(256), 0, s, N, M, dpl, (size_t)dp, B.x, M, g, B.y);
+    ZK_CHECK(hipGetLastError());
+    div_cyclic_product(dev, curve, lgq, B);  // 2m - 1 <= N: nothing wraps
+    hipLaunchKernelGGL(k_div_rev_trunc, dim3(copy_grid(2 * M)), dim3(256), 0, s, M, B.x, dqo);
+    ZK_CHECK(hipGetLastError());
+  }
+  mark(2);
+  // ---- remainder: fold(p) - fold(q) fold(d) mod x^N - 1, N >= dq
+  if (want_rem) {
+    const size_t N = (size_t)1 << lgr;
+    div_fold<F>(s, dpl, (size_t)dp + 1, N, B.z, B.fx, B.fg);
+    div_fold<F>(s, dqo, M, N, B.x, B.fx, B.fg);
+    div_fold<F>(s, ddv, (size_t)dq + 1, N, B.y, B.fx, B.fg);
+    uint64_t gen[4];
+    zkg_fft_generator(curve, lgr, gen);
+    // fold(p) stays in z: the pointwise product goes back into x and the inverse transform into y
+    ntt_enqueue(dev, curve, lgr, gen, B.x, B.fx, B.scratch, false);
+    ntt_enqueue(dev, curve, lgr, gen, B.y, B.fg, B.scratch, false);
+    arr_mul_enqueue(dev, curve, N, B.fx, B.fg, B.x);
+    ntt_enqueue(dev, curve, lgr, gen, B.x, B.y, B.scratch, true);
+    hipLaunchKernelGGL(k_div_rem<F>, dim3(copy_grid((size_t)dq)), dim3(256), 0, s, (size_t)dq, B.z, B.y, dro);
+    ZK_CHECK(hipGetLastError());
+  }
+  mark(3);
+  // ---- write-out: the tails are zero (poly_mont.c:273-274)
+  zero_rows(quot, M, (size_t)nquot);
+  zero_rows(rem, (size_t)dq, (size_t)nrem);
+  if (host_io) {
+    if (quot) copy_to_host(dev, s, quot, dqo, M * 32);
+    if (want_rem) copy_to_host(dev, s, rem, dro, (size_t)dq * 32);
+  }
+  ZK_CHECK(hipStreamSynchronize(s));
+  if (prof) {
+    float ms[3];
+    for (int i = 0; i < 3; i++) ZK_CHECK(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+    for (int i = 0; i < 4; i++) ZK_CHECK(hipEventDestroy(ev[i]));
+    std::lock_guard<std::mutex> lock(g_div_phase_mu);
+    for (int i = 0; i < 3; i++) g_div_phase_ms[i] = ms[i];
+  }
+  g_last_div_steps.store(steps);
+  return 0;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------- public
@@ -528,6 +971,27 @@ void poly_lincomb(int curve, int K, const int *ns, const uint64_t *coeffs, const
   std::lock_guard<std::mutex> lock(dev.mu);
   if (curve == 0) poly_lincomb_t<CfgBN>(dev, K, ns, coeffs, polys, tgt, host_io);
   else poly_lincomb_t<CfgBLS>(dev, K, ns, coeffs, polys, tgt, host_io);
+}
+int poly_long_div(int curve, int n1, const uint64_t *p, int n2, const uint64_t *d, int nquot, uint64_t *quot, int nrem,
+                  uint64_t *rem, bool host_io) {
+  // refusals on the lengths alone, before a pointer is read or a device is opened
+  g_last_div_steps.store(-1);
+  if (curve != 0 && curve != 1) return -1;
+  if (n1 < 0 || n2 < 0 || (quot && nquot < 0) || (rem && nrem < 0)) return -1;
+  if (n1 > (1 << (POLY_MUL_MAX_LOG[curve] - 1))) return -1;
+  Device &dev = current_device();
+  std::lock_guard<std::mutex> lock(dev.mu);
+  return curve == 0 ? poly_div_t<CfgBN>(dev, curve, n1, p, n2, d, nquot, quot, nrem, rem, host_io)
+                    : poly_div_t<CfgBLS>(dev, curve, n1, p, n2, d, nquot, quot, nrem, rem, host_io);
+}
+void poly_set_div_base_max(int len) { g_div_base.store(len < 0 ? -1 : len); }
+int poly_div_base_max() { return div_base_in_force(); }
+int poly_div_plan(int m, int *prec, int cap) { return div_plan(m, div_base_in_force(), prec, prec ? cap : 0); }
+int poly_last_div_steps() { return g_last_div_steps.load(); }
+void poly_div_profile(int on) { g_div_profile.store(on); }
+void poly_last_div_phase_ms(double *ms) {
+  std::lock_guard<std::mutex> lock(g_div_phase_mu);
+  for (int i = 0; i < 3; i++) ms[i] = g_div_phase_ms[i];
 }
 void poly_set_mul_direct_max(int len) { g_direct_max.store(len < 0 ? -1 : len); }
 int poly_last_mul_path() { return g_last_path.load(); }

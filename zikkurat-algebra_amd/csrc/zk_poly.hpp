@@ -34,4 +34,27 @@ void poly_lincomb(int curve, int K, const int *ns, const uint64_t *coeffs, const
 void poly_set_mul_direct_max(int len);
 int poly_last_mul_path();
 
+// p = quot * d + rem with deg rem < deg d: the contract of <C>_poly_mont_long_div
+// (bls12_381_poly_mont.c:249-297), computed by Newton inversion of the reversed divisor over the
+// NTT.  Host or device pointers (host_io); quot and / or rem may be null (the reference's rem and
+// quot) and are then never touched; with dp, dq the degrees, quot[0, dp - dq] and rem[0, dq) are
+// written and the rest of nquot / nrem rows is zero; dq < 0 zeroes both; dp < dq gives quotient 0 and
+// remainder p.  Returns 0, or -1 with nothing written for a negative length, quot with
+// nquot < dp - dq + 1, rem with nrem < dq (nrem < dp + 1 when dp < dq), or
+// n1 > 2^(POLY_MUL_MAX_LOG - 1) -- that last check before any pointer is read or a device is opened.
+int poly_long_div(int curve, int n1, const uint64_t *p, int n2, const uint64_t *d, int nquot, uint64_t *quot, int nrem,
+                  uint64_t *rem, bool host_io);
+// test hooks.  Terms of the series inverse's base kernel (< 0: the default, 0 and 1: one term,
+// above the kernel's capacity: the capacity) and the value in force; the precision plan for a
+// quotient of m coefficients (returns the Newton steps s, writes prec[0 .. s] up to cap entries; -1
+// for m <= 0; no GPU call); the Newton steps of the most recent division (-1: it took an early exit)
+void poly_set_div_base_max(int len);
+int poly_div_base_max();
+int poly_div_plan(int m, int *prec, int cap);
+int poly_last_div_steps();
+// timing hook (tools/poly_div_time.py): while on, a division records HIP events around its three
+// phases; ms[0..2] = series inverse, quotient, remainder of the most recent profiled division
+void poly_div_profile(int on);
+void poly_last_div_phase_ms(double *ms);
+
 }  // namespace zk

@@ -77,6 +77,10 @@ REFERENCE_SYMBOLS += [f"{c}_poly_mont_{o}" for c in CURVES for o in POLY_OPS]
 EXTENSION_SYMBOLS += ["zkg_poly_mul_device", "zkg_poly_eval_device", "zkg_poly_lincomb_device",
                       "zkg_poly_set_mul_direct_max", "zkg_poly_last_mul_path"]
 POLY_MUL_MAX_LOG = {"bn128": 28, "bls12_381": 30}   # largest product, log2 of n1 + n2 - 1
+# division with remainder (<C>_poly_mont_{long_div,quot,rem}, poly_mont.c:249-309, as zkg_ entries)
+EXTENSION_SYMBOLS += ["zkg_poly_long_div_device", "zkg_poly_long_div", "zkg_poly_set_div_base_max",
+                      "zkg_poly_div_base_max", "zkg_poly_div_plan", "zkg_poly_last_div_steps",
+                      "zkg_poly_div_profile", "zkg_poly_last_div_phase_ms"]
 # coset and batched NTT
 EXTENSION_SYMBOLS += ["zkg_ntt_ext_device", "zkg_ntt_ext", "zkg_ntt_ext_set_max_grid"]
 # cache hooks of the NTT twiddle and shift tables
@@ -144,6 +148,16 @@ def load():
         lib.zkg_poly_eval_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, U64P, U64P]
         lib.zkg_poly_lincomb_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), U64P,
                                                 ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]
+        if hasattr(lib, "zkg_poly_long_div"):  # absent from an older variant build, as above
+            lib.zkg_poly_long_div_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                     ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                     ctypes.c_void_p]
+            lib.zkg_poly_long_div.argtypes = [ctypes.c_int, ctypes.c_int, U64P, ctypes.c_int, U64P, ctypes.c_int, U64P,
+                                              ctypes.c_int, U64P]
+            lib.zkg_poly_set_div_base_max.argtypes = [ctypes.c_int]
+            lib.zkg_poly_div_plan.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+            lib.zkg_poly_div_profile.argtypes = [ctypes.c_int]
+            lib.zkg_poly_last_div_phase_ms.argtypes = [ctypes.POINTER(ctypes.c_double)]
         lib.zkg_arr_op_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, U64P, U64P, ctypes.c_void_p]
         lib.zkg_arr_dot_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, U64P]
@@ -804,6 +818,38 @@ def poly_degree(curve, a):
     return int(_poly(curve, "degree")(a.shape[0], _p(a)))
 
 
+def _long_div(curve, p, d, want_q, want_r):
+    p, d = _fr(p), _fr(d)
+    require_gpu()
+    n1, deg = p.shape[0], poly_degree(curve, d)
+    if n1 > (1 << (POLY_MUL_MAX_LOG[curve] - 1)):
+        raise ValueError(f"poly_long_div: more than 2^{POLY_MUL_MAX_LOG[curve] - 1} coefficients")
+    nq, nr = max(0, n1 - deg), max(0, deg)  # the Haskell sizes (Poly.hs:322-334)
+    q = np.zeros((nq, 4), dtype=np.uint64) if want_q else None
+    r = np.zeros((nr, 4), dtype=np.uint64) if want_r else None
+    rc = load().zkg_poly_long_div(CURVE_ID[curve], n1, _p(p), d.shape[0], _p(d), nq, _p(q) if want_q else None,
+                                  nr, _p(r) if want_r else None)
+    if rc != 0:
+        raise RuntimeError("zkg_poly_long_div refused the call")
+    return q, r
+
+
+def poly_long_div(curve, p, d):
+    """Poly.polyLongDiv (Poly.hs:322-334): (quotient, remainder) with p = q * d + r, deg r < deg d, bit-identical
+    to the reference's schoolbook loop (zkg_poly_long_div: Newton inversion over the NTT)"""
+    return _long_div(curve, p, d, True, True)
+
+
+def poly_quot(curve, p, d):
+    """Poly.polyQuot: the quotient alone (the remainder is not computed)"""
+    return _long_div(curve, p, d, True, False)[0]
+
+
+def poly_rem(curve, p, d):
+    """Poly.polyRem: the remainder alone"""
+    return _long_div(curve, p, d, False, True)[1]
+
+
 ARR_OP_CODE = {"neg": 0, "add": 1, "sub": 2, "sub_rev": 3, "sqr": 4, "mul": 5, "mul_add": 6, "mul_sub": 7,
                "scale": 8, "Ax_plus_y": 9, "Ax_plus_By": 10, "from_std": 11, "to_std": 12, "copy": 13,
                "set_const": 14, "inv": 15, "div": 16}
@@ -919,6 +965,39 @@ def poly_lincomb_device(curve, ns, coeffs, d_polys, d_tgt):
     cn = (ctypes.c_int * max(1, K))(*ns)
     pp = (ctypes.c_void_p * max(1, K))(*[d.ptr for d in d_polys])
     load().zkg_poly_lincomb_device(CURVE_ID[curve], K, cn, _p(cs), pp, d_tgt.ptr if d_tgt else None)
+
+
+def poly_long_div_device(curve, n1, d_p, n2, d_d, nquot, d_quot, nrem, d_rem):
+    """device-resident division (zkg_poly_long_div_device): 0, or -1 when the call is refused; d_quot and / or
+    d_rem may be None (the remainder / the quotient alone)"""
+    return load().zkg_poly_long_div_device(CURVE_ID[curve], n1, d_p.ptr if d_p else None, n2, d_d.ptr if d_d else None,
+                                           nquot, d_quot.ptr if d_quot else None, nrem, d_rem.ptr if d_rem else None)
+
+
+def poly_set_div_base_max(length):
+    """test hook: terms of the series inverse's base kernel (< 0: the default, 0 / 1: one term)"""
+    load().zkg_poly_set_div_base_max(int(length))
+
+
+def poly_div_base_max():
+    """the base kernel size in force (after clamping to the kernel's capacity)"""
+    return load().zkg_poly_div_base_max()
+
+
+def poly_div_plan(m):
+    """the precisions [base terms, after step 1, ..., m] of the series inverse for a quotient of m coefficients
+    (len - 1 Newton steps), or None for m <= 0; a host computation"""
+    s = load().zkg_poly_div_plan(int(m), None, 0)
+    if s < 0:
+        return None
+    prec = (ctypes.c_int * (s + 1))()
+    load().zkg_poly_div_plan(int(m), prec, s + 1)
+    return list(prec)
+
+
+def poly_last_div_steps():
+    """Newton steps of the most recent division, -1 when it took an early exit"""
+    return load().zkg_poly_last_div_steps()
 
 
 def poly_set_mul_direct_max(length):
