@@ -365,7 +365,17 @@ ZKG_API int zkg_ntt_ext(int curve, int inverse, int m, const uint64_t *gen, cons
 /* device-resident Fr vector ops: d_* are DEVICE pointers, kA/kB and dot's tgt HOST.
  * op codes: 0 neg, 1 add, 2 sub, 3 sub_rev (b - a), 4 sqr, 5 mul, 6 mul_add, 7 mul_sub,
  * 8 scale (kA a), 9 Ax_plus_y, 10 Ax_plus_By, 11 from_std, 12 to_std, 13 copy,
- * 14 set_const (kA), 15 inv, 16 div (a / b) */
+ * 14 set_const (kA), 15 inv, 16 div (a / b)
+ * Aliasing (tests/test_gpu_arr_device.py): any operand may be EXACTLY the target (d_tgt == d_a, d_b or d_c;
+ * operands may also be each other), for every op code, and the result is the one of distinct buffers
+ * computed from the inputs as they were before the call -- also for mul_add / mul_sub with d_tgt == d_c
+ * and Ax_plus_y with d_tgt == d_b, where the reference's loops, aliased like that, lose the addend
+ * (arr_mont.c:124-137, 204-209).  Partial overlap (a target shifted against an input) is undefined.
+ * Nothing outside rows [0, n) of the target is written, and no input that is not the target is written;
+ * powers with n == 0 writes nothing.  dot's operands may be the same buffer.  div_by_vanishing writes
+ * exactly nquot / nrem rows (zero past deg - expo_n + 1 quotient and expo_n remainder rows, as the
+ * reference does), aliases nothing, and with d_rem == NULL returns 1 when the remainder is zero, else 0.
+ * The G1 conversions below (rows of 3 NP words in, 2 NP words out) need distinct buffers. */
 ZKG_API void zkg_arr_op_device(int curve, int op, int n, const uint64_t *d_a, const uint64_t *d_b,
                                const uint64_t *d_c, const uint64_t *kA, const uint64_t *kB, uint64_t *d_tgt);
 ZKG_API void zkg_arr_dot_device(int curve, int n, const uint64_t *d_a, const uint64_t *d_b, uint64_t *tgt);

@@ -129,10 +129,14 @@ class Oracle:
                                 _p(out))
         return out
 
-    def div_by_vanishing(self, curve, poly, n, eta):
+    def div_by_vanishing(self, curve, poly, n, eta, nquot=None, nrem=None):
+        """(quotient, remainder, remainder is zero) by x^n - eta in buffers of nquot / nrem rows (default
+        n1 - n and n; the caller keeps nquot >= deg - n + 1 and nrem >= n, poly_mont.c:321-322): rows
+        past the quotient's / remainder's length are zero"""
         n1 = poly.shape[0]
-        nq, nr = max(0, n1 - n), max(0, n)
-        q = np.zeros((max(nq, 1), 4), dtype=np.uint64)
+        nq = max(0, n1 - n) if nquot is None else nquot
+        nr = max(0, n) if nrem is None else nrem
+        q =np.zeros((max(nq, 1), 4), dtype=np.uint64)
         r = np.zeros((max(nr, 1), 4), dtype=np.uint64)
         ok = self.lib.zko_div_by_vanishing(self._c(curve), n1, _p(poly), n, _p(np.ascontiguousarray(eta)), nq,
                                            _p(q), nr, _p(r))

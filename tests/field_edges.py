@@ -543,3 +543,76 @@ def fft_inputs(zk, oracle, curve, coords, m):
         const.append((M.mul1(x, Z), M.mul1(y, Z), Z) if coords == "proj" else (M.mul1(x, Z2), M.mul1(y, M.mul1(Z2, Z)), Z))
     out.append(("constant", np.tile(aff[0], (n, 1)), point_rows(const, nl)))
     return out
+
+
+# ---------------------------------------------------------------------------- predicates (shared by the CPU and GPU tests)
+PRED_N = (1, 256, 257)
+PRED_STRIDE = 4096 * 256  # threads of k_pred's largest grid: rows from here on are reached by its grid-stride loop
+PRED_N_LARGE = PRED_STRIDE + 259
+PREDICATES = ("is_valid", "is_zero", "is_one", "is_equal")
+
+
+def valid_rows(curve, n, seed):
+    """(n, 4) canonical rows without a Python loop: random low limbs under a top limb below r's own"""
+    rng = np.random.default_rng(seed)
+    a = rng.integers(0, 1 << 64, size=(n, 4), dtype=np.uint64)
+    a[:, 3] = rng.integers(0, FR[curve] >> 192, size=n, dtype=np.uint64)
+    return a
+
+
+def pred_positions(n):
+    """where the offending row goes: first, last, and the second row of the grid-stride loop's second trip"""
+    return sorted({0, n - 1} | ({PRED_STRIDE + 1} if n > PRED_STRIDE + 1 else set()))
+
+
+def is_valid_plants(curve):
+    """[(name, row, verdict of is_valid on an otherwise valid array)]: the boundary x < r"""
+    r = FR[curve]
+    up = to_row(r, 4).copy()
+    up[0] += np.uint64(1)  # r with only limb 0 raised by one
+    return [("r_minus_1", to_row(r - 1, 4), True), ("r", to_row(r, 4), False), ("r_plus_1", to_row(r + 1, 4), False),
+            ("all_ones", to_row(M256, 4), False), ("r_limb0_up", up, False)]
+
+
+def pred_cases(curve, n, positions, full=True, seed=0x9ED1):
+    """yields (label, predicate, operands, expected verdict).  One clean case per predicate (valid rows;
+    all zero; all the Montgomery one; an array and its copy), then one offending row at each position:
+    is_valid the rows of is_valid_plants, is_zero / is_one a row that differs from the constant in
+    exactly one limb (each of the four in turn, one bit of it), is_equal a second array that differs in
+    one bit of one limb of that row.  full=False keeps one offending variant per predicate."""
+    r = FR[curve]
+    a = valid_rows(curve, n, seed)
+    zero = np.zeros((n, 4), dtype=np.uint64)
+    one = np.tile(to_row(radix(r) % r, 4), (n, 1))
+    yield "clean", "is_valid", (a,), True
+    yield "clean", "is_zero", (zero,), True
+    yield "clean", "is_one", (one,), True
+    yield "clean", "is_equal", (a, a.copy()), True
+    bits = (0, 63, 31, 62)  # the bit flipped in limb j
+    for pos in positions:
+        for name, row, verdict in is_valid_plants(curve) if full else is_valid_plants(curve)[1:2]:
+            x = a.copy()
+            x[pos] = row
+            yield f"{name}@{pos}", "is_valid", (x,), verdict
+        for j in range(4) if full else (3,):
+            flip = np.uint64(1) << np.uint64(bits[j])
+            for pred, base in (("is_zero", zero), ("is_one", one)):
+                x = base.copy()
+                x[pos, j] ^= flip
+                yield f"limb{j}@{pos}", pred, (x,), False
+            y = a.copy()
+            y[pos, j] ^= flip
+            yield f"limb{j}@{pos}", "is_equal", (a, y), False
+
+
+def pred_model(curve, pred, ops):
+    """the predicate on Python integers"""
+    r = FR[curve]
+    x = from_limbs(ops[0])
+    if pred == "is_valid":
+        return all(v < r for v in x)
+    if pred == "is_zero":
+        return all(v == 0 for v in x)
+    if pred == "is_one":
+        return all(v == radix(r) % r for v in x)
+    return x == from_limbs(ops[1])

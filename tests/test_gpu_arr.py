@@ -6,6 +6,8 @@ import ctypes
 import numpy as np
 import pytest
 
+import field_edges as fe
+
 pytestmark = pytest.mark.gpu
 CURVES = ["bn128", "bls12_381"]
 
@@ -175,6 +177,37 @@ def test_quot_by_vanishing_exact(gpu, curve):
     p[:m] = gpu.arr_sub(curve, p[:m].copy(), gpu.arr_scale(curve, eta, g))
     q = gpu.quot_by_vanishing(curve, p, n, eta)
     assert q is not None and np.array_equal(q, g)
+
+
+def _pred(gpu, curve, pred, ops):
+    return getattr(gpu, "arr_" + pred)(curve, *ops)
+
+
+@pytest.mark.parametrize("curve", CURVES)
+@pytest.mark.parametrize("n", fe.PRED_N)
+def test_predicate_single_offending_row(gpu, curve, n):
+    """k_pred with ONE offending row, first or last, in an otherwise passing array (field_edges.pred_cases;
+    tests/test_arr_predicates_cpu.py checks the verdicts against the reference's C and Python integers):
+    is_valid at r - 1 (valid), r, r + 1, 2^256 - 1 and r with only limb 0 raised; is_zero and is_one with
+    a row that differs from the constant in one bit of one limb, each limb in turn; is_equal with two
+    arrays that differ in one bit of one limb"""
+    for label, pred, ops, want in fe.pred_cases(curve, n, fe.pred_positions(n)):
+        assert _pred(gpu, curve, pred, ops) == want, (pred, label)
+
+
+@pytest.mark.parametrize("curve", CURVES)
+@pytest.mark.parametrize("pred", fe.PREDICATES)
+def test_predicate_grid_stride_loop(gpu, curve, pred):
+    """n = 4096 * 256 + 259: the rows past the 4096-block grid are reached by k_pred's stride loop.  The
+    clean array passes; one offending row at 4096 * 256 + 1 (second trip of the loop), at 0 or at n - 1
+    fails -- one variant per predicate"""
+    n = fe.PRED_N_LARGE
+    ran = []
+    for label, p, ops, want in fe.pred_cases(curve, n, fe.pred_positions(n), full=False):
+        if p == pred:
+            assert _pred(gpu, curve, pred, ops) == want, (pred, label)
+            ran.append(label)
+    assert len(ran) == 4 and any(label.endswith(f"@{fe.PRED_STRIDE + 1}") for label in ran)
 
 
 @pytest.mark.parametrize("curve", CURVES)

@@ -93,6 +93,45 @@ def test_div_by_vanishing_vs_reference(oracle, reference, curve, n1, n, eta_one)
 
 
 @pytest.mark.parametrize("curve", CURVES)
+@pytest.mark.parametrize("n1,n", [(40, 8), (7, 8), (100, 32)])
+def test_div_by_vanishing_buffer_sizes_vs_reference(oracle, reference, curve, n1, n):
+    """the smallest legal buffers (deg - n + 1 quotient rows, n remainder rows) and five rows more of
+    each: the reference zeroes the rows past the quotient and the remainder (poly_mont.c:327-337), and
+    so does the oracle with the same nquot / nrem"""
+    poly = fr(oracle, curve, 21 + n1, n1)
+    poly[-2:] = 0
+    eta = fr(oracle, curve, 22, 1)[0]
+    deg = n1 - 3
+    nq0 = max(0, deg - n + 1)
+    for extra in (0, 5):
+        nq, nr = nq0 + extra, n + extra
+        q, r, _ = oracle.div_by_vanishing(curve, poly, n, eta, nquot=nq, nrem=nr)
+        assert q.shape == (nq, 4) and r.shape == (nr, 4)
+        wq = np.ones((max(nq, 1), 4), dtype=np.uint64)
+        wr = np.ones((nr, 4), dtype=np.uint64)
+        reference.arr(curve, "poly_mont_div_by_vanishing", n1, poly, n, eta, nq, wq, nr, wr)
+        assert np.array_equal(q, wq[:nq]) and np.array_equal(r, wr)
+        assert not q[nq0:].any() and not r[n:].any()
+
+
+@pytest.mark.parametrize("curve", CURVES)
+@pytest.mark.parametrize("n1,n", [(40, 8), (7, 8), (100, 32)])
+def test_div_by_vanishing_buffer_sizes(oracle, curve, n1, n):
+    """nquot / nrem only cut or zero-extend the default buffers (n1 - n and n rows)"""
+    poly = fr(oracle, curve, 21 + n1, n1)
+    poly[-2:] = 0
+    eta = fr(oracle, curve, 22, 1)[0]
+    nq0 = max(0, n1 - 3 - n + 1)
+    q, r, ok = oracle.div_by_vanishing(curve, poly, n, eta)
+    assert not q[nq0:].any()
+    for nq, nr in ((nq0, n), (nq0 + 5, n + 5)):
+        q2, r2, ok2 = oracle.div_by_vanishing(curve, poly, n, eta, nquot=nq, nrem=nr)
+        assert ok2 == ok and q2.shape == (nq, 4) and r2.shape == (nr, 4)
+        assert np.array_equal(q2[:nq0], q[:nq0]) and not q2[nq0:].any()
+        assert np.array_equal(r2[:n], r) and not r2[n:].any()
+
+
+@pytest.mark.parametrize("curve", CURVES)
 def test_exact_multiple_quotient(oracle, reference, curve):
     """(x^n - eta) * g(x) divides exactly: quot_by_vanishing finds g, remainder zero"""
     n, m = 16, 24

@@ -162,6 +162,11 @@ def load():
                                           ctypes.c_void_p, U64P, U64P, ctypes.c_void_p]
         lib.zkg_arr_dot_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, U64P]
         lib.zkg_arr_powers_device.argtypes = [ctypes.c_int, ctypes.c_int, U64P, U64P, ctypes.c_void_p]
+        lib.zkg_poly_div_by_vanishing_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                         U64P, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                         ctypes.c_void_p]
+        for f in (lib.zkg_g1_batch_to_affine_device, lib.zkg_g1_jac_batch_to_affine_device):
+            f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         lib.zkg_last_error.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         lib.zkg_comm_unique_id.argtypes = [ctypes.c_void_p]
         lib.zkg_comm_init.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
@@ -944,6 +949,33 @@ def arr_op_device(curve, op, n, d_a, d_b=None, d_c=None, kA=None, kB=None, d_tgt
     kb = np.ascontiguousarray(kB if kB is not None else z, dtype=np.uint64)
     load().zkg_arr_op_device(CURVE_ID[curve], ARR_OP_CODE[op], n, d_a.ptr if d_a else None,
                              d_b.ptr if d_b else None, d_c.ptr if d_c else None, _p(ka), _p(kb), d_tgt.ptr)
+
+
+def arr_dot_device(curve, n, d_a, d_b):
+    """device-resident dot product (zkg_arr_dot_device): the Montgomery Fr sum of a_i b_i; d_a may be d_b"""
+    out = np.zeros(4, dtype=np.uint64)
+    load().zkg_arr_dot_device(CURVE_ID[curve], n, d_a.ptr, d_b.ptr, _p(out))
+    return out
+
+
+def arr_powers_device(curve, n, kA, kB, d_tgt):
+    """d_tgt[i] = kA kB^i, i < n (zkg_arr_powers_device); n == 0 writes nothing"""
+    load().zkg_arr_powers_device(CURVE_ID[curve], n, _p(_k(kA)), _p(_k(kB)), d_tgt.ptr)
+
+
+def div_by_vanishing_device(curve, n1, d_src, expo_n, eta, nquot, d_quot, nrem=0, d_rem=None):
+    """device-resident division by x^expo_n - eta (zkg_poly_div_by_vanishing_device): nquot / nrem rows are
+    written, zero past the quotient's / remainder's length.  With d_rem None the return value is 1 when the
+    remainder is zero, else 0 (quot_by_vanishing)."""
+    return load().zkg_poly_div_by_vanishing_device(CURVE_ID[curve], n1, d_src.ptr, expo_n, _p(_k(eta)), nquot,
+                                                   d_quot.ptr, nrem, d_rem.ptr if d_rem else None)
+
+
+def batch_to_affine_device(curve, n, d_src, d_tgt, coords="proj"):
+    """device-resident batchToAffine (zkg_g1_batch_to_affine_device / zkg_g1_jac_batch_to_affine_device): n rows
+    of 3 NP words -> n rows of 2 NP words; distinct buffers"""
+    f = load().zkg_g1_batch_to_affine_device if _coords(coords) == "proj" else load().zkg_g1_jac_batch_to_affine_device
+    f(CURVE_ID[curve], n, d_src.ptr, d_tgt.ptr)
 
 
 def poly_mul_device(curve, n1, d_a, n2, d_b, d_tgt):
