@@ -25,17 +25,15 @@
 // 2^24 elements: a product costs ~170 mads, the VALU sustains ~1.5e11 Fr products/s,
 // i.e. ~2 products per 64 B of traffic at 8 TB/s).  Batch inversion is a chunked
 // Montgomery trick: CHK consecutive elements per lane, one Fermat inversion per chunk.
+//
+// Shared with zk_poly.hip: the row helpers, block_sum and k_dot_final (zk_frdev.hpp),
+// CfgBN / CfgBLS, with_fr and PowSplit (zk_frcfg.hpp), Stage and read_back (zk_runtime.hpp).
 #include <hipcub/hipcub.hpp>
-#include "zk_field.hpp"
-#include "zk_host.hpp"
-#include "zk_runtime.hpp"
+#include "zk_frdev.hpp"
+#include "zk_frcfg.hpp"
 #include "zk_arr.hpp"
 
 namespace zk {
-
-struct U256 {
-  uint64_t w[4];
-};
 
 struct ArrArgs {
   int op, n;
@@ -44,28 +42,6 @@ struct ArrArgs {
   U256 kA, kB;   // coefficients (reference form)
   U256 cstd;     // R * R' mod p: from_std constant (x -> x R in one product)
 };
-
-template <class F>
-__device__ __forceinline__ void ld(Fe<F> &x, const uint64_t *p, size_t i) { fe_load_ref(x, p + i * 4); }
-template <class F>
-__device__ __forceinline__ void st(uint64_t *p, size_t i, const Fe<F> &x) { fe_store_ref(p + i * 4, x); }
-template <class F>
-__device__ __forceinline__ void ld_const(Fe<F> &x, const U256 &k) {
-  uint32_t w[8];
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    w[2 * j] = (uint32_t)k.w[j];
-    w[2 * j + 1] = (uint32_t)(k.w[j] >> 32);
-  }
-  fe_unpack(x, w);
-}
-// reference-form product: (xR)(yR) -> xyR
-template <class F>
-__device__ __forceinline__ void mul_ref(Fe<F> &r, const Fe<F> &a, const Fe<F> &b) {
-  Fe<F> t;
-  fe_mul(t, a, b);
-  fe_to_int(r, t);
-}
 
 template <class F>
 __global__ void __launch_bounds__(256) k_arr_map(ArrArgs g) {
@@ -485,7 +461,6 @@ __global__ void k_pred(int pred, int n, const uint64_t *__restrict__ a, const ui
 
 // ---------------------------------------------------------------------------- dot product
 
-constexpr int DOT_THREADS = 256;
 template <class F>
 __global__ void __launch_bounds__(DOT_THREADS) k_dot(int n, const uint64_t *__restrict__ a,
                                                      const uint64_t *__restrict__ b, uint64_t *__restrict__ part) {
@@ -501,57 +476,16 @@ __global__ void __launch_bounds__(DOT_THREADS) k_dot(int n, const uint64_t *__re
     fe_add(s, acc, z);
     acc = s;
   }
-  for (int q = 0; q < F::N; q++) lds[threadIdx.x * F::N + q] = acc.v[q];
-  __syncthreads();
-  for (int s = DOT_THREADS / 2; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      Fe<F> o, r;
-      for (int q = 0; q < F::N; q++) o.v[q] = lds[(threadIdx.x + s) * F::N + q];
-      fe_add(r, acc, o);
-      acc = r;
-      for (int q = 0; q < F::N; q++) lds[threadIdx.x * F::N + q] = acc.v[q];
-    }
-    __syncthreads();
-  }
+  block_sum(acc, lds);
   if (threadIdx.x == 0) st(part, blockIdx.x, acc);  // canonical, still in the R^2/R' form
 }
-// the block partials' sum: one 256-thread block, each thread adding every 256th partial, then the
-// same LDS tree as k_dot (round 5 summed the 1024 partials on ONE thread: 0.34 ms of a 0.55 ms
-// 2^24 dot product, profiles/r06c_prof)
-template <class F>
-__global__ void __launch_bounds__(DOT_THREADS) k_dot_final(int nparts, const uint64_t *__restrict__ part,
-                                                           uint64_t *__restrict__ out) {
-  __shared__ uint32_t lds[DOT_THREADS * F::N];
-  Fe<F> acc;
-  fe_zero(acc);
-  for (int i = threadIdx.x; i < nparts; i += DOT_THREADS) {
-    Fe<F> x, s;
-    ld(x, part, i);
-    fe_add(s, acc, x);
-    acc = s;
-  }
-  for (int q = 0; q < F::N; q++) lds[threadIdx.x * F::N + q] = acc.v[q];
-  __syncthreads();
-  for (int s = DOT_THREADS / 2; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      Fe<F> o, r;
-      for (int q = 0; q < F::N; q++) o.v[q] = lds[(threadIdx.x + s) * F::N + q];
-      fe_add(r, acc, o);
-      acc = r;
-      for (int q = 0; q < F::N; q++) lds[threadIdx.x * F::N + q] = acc.v[q];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    Fe<F> r;
-    fe_to_int(r, acc);  // x y R^2/R' * R'/R = x y R (the product by 32 on the 9 x 29-bit fields)
-    st(out, 0, r);
-  }
-}
+// the block partials' sum and the closing conversion: k_dot_final<F, true> (zk_frdev.hpp)
 
 // ---------------------------------------------------------------------------- powers
 
-// tlo[i] = B^i (internal, i < 2^h);  thi[j] = A * B^(j 2^h) (reference form)
+// tlo[i] = B^i (internal, i < 2^h);  thi[j] = A * B^(j 2^h) (reference form).  The two square-and-
+// multiply loops are written out: through a helper shared with zk_poly.hip's fe_pow_u32 this kernel
+// compiles to other instructions ("Fr units")
 template <class F>
 __global__ void k_pow_tables(int h, int nlo, int nhi, U256 kA, U256 kB, uint64_t *__restrict__ tlo,
                              uint64_t *__restrict__ thi) {
@@ -750,9 +684,6 @@ __global__ void __launch_bounds__(256) k_vanish_rem(int deg, int n, const uint64
 
 // ---------------------------------------------------------------------------- host side
 
-struct CfgBN { using Fd = BN_Fr; using Fh = zkh::BN_Fr; };
-struct CfgBLS { using Fd = BLS_Fr; using Fh = zkh::BLS_Fr; };
-
 template <class Fh>
 static U256 to_u256(const zkh::Fe<Fh> &x) {
   U256 u;
@@ -794,23 +725,6 @@ static unsigned grid_for(size_t n) {
   if (b > 4096) b = 4096;  // grid-stride loops beyond ~16 waves per SIMD
   return (unsigned)(b ? b : 1);
 }
-
-// staging of host operands: every array is copied into the call's arena
-struct Stage {
-  Device &dev;
-  bool host;
-  explicit Stage(Device &d, bool h) : dev(d), host(h) {}
-  const uint64_t *in(const uint64_t *p, size_t n) {
-    if (!host || !p) return p;
-    uint64_t *d = dev.arena.take<uint64_t>(n * 4);
-    if (n) ZK_CHECK(hipMemcpyAsync(d, p, n * 32, hipMemcpyHostToDevice, dev.stream));
-    return d;
-  }
-  uint64_t *out(uint64_t *p, size_t n) { return host ? dev.arena.take<uint64_t>(n * 4) : p; }
-  void back(uint64_t *host_p, const uint64_t *dev_p, size_t n) {  // waits (pinned pieces for large outputs)
-    if (host && n) copy_to_host(dev, dev.stream, host_p, dev_p, n * 32);
-  }
-};
 
 // ZK_ARR_STAGE (A/B hook; default: 4 for the streaming ops, 2 for the ops with a product per
 // element): 2 staged + nontemporal, 4 the same software-pipelined (every array's runs fetched before
@@ -939,28 +853,31 @@ static void arr_op_t(Device &dev, int op, int n, const uint64_t *a, const uint64
   ZK_CHECK(hipStreamSynchronize(st));
 }
 
+// 1 when every element of the device rows da[0, n) (against db) passes `pred`: the flag's clear, the
+// launch and the wait for the verdict
+static int run_pred(Device &dev, int pred, size_t n, const uint64_t *da, const uint64_t *db, const U256 &prime,
+                    const U256 &one) {
+  uint32_t *fail = dev.arena.take<uint32_t>(1);
+  ZK_CHECK(hipMemsetAsync(fail, 0, 4, dev.stream));
+  if (n) {
+    hipLaunchKernelGGL(k_pred, dim3(grid_for(n)), dim3(256), 0, dev.stream, pred, (int)n, da, db, prime, one, fail);
+    ZK_CHECK(hipGetLastError());
+  }
+  return *read_back(dev, fail) ? 0 : 1;
+}
+
 template <class Cfg>
 static int arr_pred_t(Device &dev, int pred, int n, const uint64_t *a, const uint64_t *b, bool host_io) {
   using Fh = typename Cfg::Fh;
-  hipStream_t st = dev.stream;
   const size_t N = (size_t)(n > 0 ? n : 0);
   dev.arena.reserve(N * 32 * 2 + (1 << 20));
   dev.arena.reset();
   Stage sg(dev, host_io);
   const uint64_t *da = sg.in(a, N);
   const uint64_t *db = pred == PRED_IS_EQUAL ? sg.in(b, N) : nullptr;
-  uint32_t *fail = dev.arena.take<uint32_t>(1);
-  ZK_CHECK(hipMemsetAsync(fail, 0, 4, st));
   U256 prime, one;
   for (int j = 0; j < 4; j++) { prime.w[j] = Fh::P[j]; one.w[j] = Fh::ONE[j]; }
-  if (N) {
-    hipLaunchKernelGGL(k_pred, dim3(grid_for(N)), dim3(256), 0, st, pred, n, da, db, prime, one, fail);
-    ZK_CHECK(hipGetLastError());
-  }
-  uint32_t *h = reinterpret_cast<uint32_t *>(dev.host_staging(4));
-  ZK_CHECK(hipMemcpyAsync(h, fail, 4, hipMemcpyDeviceToHost, st));
-  ZK_CHECK(hipStreamSynchronize(st));
-  return *h ? 0 : 1;
+  return run_pred(dev, pred, N, da, db, prime, one);
 }
 
 template <class Cfg>
@@ -978,12 +895,9 @@ static void arr_dot_t(Device &dev, int n, const uint64_t *a, const uint64_t *b, 
   uint64_t *out = dev.arena.take<uint64_t>(4);
   hipLaunchKernelGGL(k_dot<F>, dim3(blocks), dim3(DOT_THREADS), 0, st, n, da, db, part);
   ZK_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_dot_final<F>, dim3(1), dim3(DOT_THREADS), 0, st, (int)blocks, part, out);
+  hipLaunchKernelGGL((k_dot_final<F, true>), dim3(1), dim3(DOT_THREADS), 0, st, (int)blocks, part, out);
   ZK_CHECK(hipGetLastError());
-  uint64_t *h = reinterpret_cast<uint64_t *>(dev.host_staging(32));
-  ZK_CHECK(hipMemcpyAsync(h, out, 32, hipMemcpyDeviceToHost, st));
-  ZK_CHECK(hipStreamSynchronize(st));
-  memcpy(tgt_host, h, 32);
+  memcpy(tgt_host, read_back(dev, out, 4), 32);
 }
 
 template <class Cfg>
@@ -992,21 +906,17 @@ static void arr_powers_t(Device &dev, int n, const uint64_t *kA, const uint64_t 
   hipStream_t st = dev.stream;
   if (n <= 0) return;  // powers: n == 0 writes nothing (arr_mont.c)
   const size_t N = (size_t)n;
-  int lg = 0;
-  while (((size_t)1 << lg) < N) lg++;
-  const int h = (lg + 1) / 2;
-  const int nlo = 1 << h, nhi = (int)((N + nlo - 1) >> h);
-  dev.arena.reserve(N * 32 + ((size_t)nlo + nhi) * 32 + (1 << 20));
+  const PowSplit ps(N);
+  dev.arena.reserve(N * 32 + ((size_t)ps.nlo + ps.nhi) * 32 + (1 << 20));
   dev.arena.reset();
   Stage sg(dev, host_io);
   uint64_t *dt = sg.out(tgt, N);
-  uint64_t *tlo = dev.arena.take<uint64_t>((size_t)nlo * 4);
-  uint64_t *thi = dev.arena.take<uint64_t>((size_t)nhi * 4);
-  const int nt = nlo > nhi ? nlo : nhi;
-  hipLaunchKernelGGL(k_pow_tables<F>, dim3(div_up(nt, 256)), dim3(256), 0, st, h, nlo, nhi, load_u256(kA),
-                     load_u256(kB), tlo, thi);
+  uint64_t *tlo = dev.arena.take<uint64_t>((size_t)ps.nlo * 4);
+  uint64_t *thi = dev.arena.take<uint64_t>((size_t)ps.nhi * 4);
+  hipLaunchKernelGGL(k_pow_tables<F>, dim3(div_up(std::max(ps.nlo, ps.nhi), 256)), dim3(256), 0, st, ps.h, ps.nlo,
+                     ps.nhi, load_u256(kA), load_u256(kB), tlo, thi);
   ZK_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_powers<F>, dim3(stream_grid(N, true)), dim3(256), 0, st, n, h, tlo, thi, dt);
+  hipLaunchKernelGGL(k_powers<F>, dim3(stream_grid(N, true)), dim3(256), 0, st, n, ps.h, tlo, thi, dt);
   ZK_CHECK(hipGetLastError());
   sg.back(tgt, dt, N);
   ZK_CHECK(hipStreamSynchronize(st));
@@ -1028,16 +938,8 @@ static int div_vanishing_t(Device &dev, int n1, const uint64_t *src, int n, cons
   uint64_t *dq = sg.out(quot, (size_t)nquot);
   uint64_t *dr = want_rem ? sg.out(rem, NR) : dev.arena.take<uint64_t>(NR * 4);
   int *ddeg = dev.arena.take<int>(1);
-  ZK_CHECK(hipMemsetAsync(ddeg, 0xff, 4, st));  // -1
-  if (N1) {
-    hipLaunchKernelGGL(k_degree, dim3((unsigned)std::min<size_t>(DEG_GRID, (N1 + DEG_CHUNK - 1) / DEG_CHUNK)), dim3(256), 0,
-                       st, n1, da, ddeg);
-    ZK_CHECK(hipGetLastError());
-  }
-  int *hdeg = reinterpret_cast<int *>(dev.host_staging(4));
-  ZK_CHECK(hipMemcpyAsync(hdeg, ddeg, 4, hipMemcpyDeviceToHost, st));
-  ZK_CHECK(hipStreamSynchronize(st));
-  const int deg = *hdeg;
+  poly_degree_enqueue(dev, n1, da, ddeg);
+  const int deg = *read_back(dev, ddeg);
   ZK_REQUIRE(nquot >= deg - n + 1, "poly_div_by_vanishing: quotient buffer too small");  // poly_mont.c:328
   ZK_REQUIRE(!want_rem || nrem >= n, "poly_div_by_vanishing: remainder buffer too small");  // :329
   const U256 e = load_u256(eta);
@@ -1073,21 +975,12 @@ static int div_vanishing_t(Device &dev, int n1, const uint64_t *src, int n, cons
     return -1;
   }
   // quot_by_vanishing: is the remainder (n coefficients) zero?
-  uint32_t *fail = dev.arena.take<uint32_t>(1);
-  ZK_CHECK(hipMemsetAsync(fail, 0, 4, st));
-  U256 z = {{0, 0, 0, 0}};
-  hipLaunchKernelGGL(k_pred, dim3(grid_for(NR)), dim3(256), 0, st, (int)PRED_IS_ZERO, (int)NR, dr, nullptr, z, z,
-                     fail);
-  ZK_CHECK(hipGetLastError());
-  uint32_t *h = reinterpret_cast<uint32_t *>(dev.host_staging(4));
-  ZK_CHECK(hipMemcpyAsync(h, fail, 4, hipMemcpyDeviceToHost, st));
-  ZK_CHECK(hipStreamSynchronize(st));
-  return *h ? 0 : 1;
+  const U256 z = {{0, 0, 0, 0}};
+  return run_pred(dev, PRED_IS_ZERO, NR, dr, nullptr, z, z);  // NR = n >= 1
 }
 
 template <class Cfg>
 static int poly_degree_t(Device &dev, int n, const uint64_t *a, bool host_io) {
-  hipStream_t st = dev.stream;
   const size_t N = (size_t)(n > 0 ? n : 0);
   if (!N) return -1;  // poly_mont.c:26-32
   dev.arena.reserve((host_io ? N * 32 : 0) + (1 << 20));
@@ -1095,14 +988,8 @@ static int poly_degree_t(Device &dev, int n, const uint64_t *a, bool host_io) {
   Stage sg(dev, host_io);
   const uint64_t *da = sg.in(a, N);
   int *ddeg = dev.arena.take<int>(1);
-  ZK_CHECK(hipMemsetAsync(ddeg, 0xff, 4, st));  // -1
-  hipLaunchKernelGGL(k_degree, dim3((unsigned)std::min<size_t>(DEG_GRID, (N + DEG_CHUNK - 1) / DEG_CHUNK)), dim3(256), 0, st,
-                     n, da, ddeg);
-  ZK_CHECK(hipGetLastError());
-  int *hdeg = reinterpret_cast<int *>(dev.host_staging(4));
-  ZK_CHECK(hipMemcpyAsync(hdeg, ddeg, 4, hipMemcpyDeviceToHost, st));
-  ZK_CHECK(hipStreamSynchronize(st));
-  return *hdeg;
+  poly_degree_enqueue(dev, n, da, ddeg);
+  return *read_back(dev, ddeg);
 }
 
 // ---------------------------------------------------------------------------- public
@@ -1114,8 +1001,9 @@ void arr_mul_enqueue(Device &dev, int curve, size_t n, const uint64_t *d_a, cons
   g.a = d_a;
   g.b = d_b;
   g.tgt = d_tgt;
-  if (curve == 0) launch_arr_op<BN_Fr>(ARR_MUL, g, dim3(stream_grid(n, true)), dev.stream);
-  else launch_arr_op<BLS_Fr>(ARR_MUL, g, dim3(stream_grid(n, true)), dev.stream);
+  with_cfg(curve, [&](auto cfg) {
+    launch_arr_op<typename decltype(cfg)::Fd>(ARR_MUL, g, dim3(stream_grid(n, true)), dev.stream);
+  });
 }
 void poly_degree_enqueue(Device &dev, int n, const uint64_t *d_a, int *d_deg) {
   ZK_CHECK(hipMemsetAsync(d_deg, 0xff, 4, dev.stream));  // -1
@@ -1126,41 +1014,27 @@ void poly_degree_enqueue(Device &dev, int n, const uint64_t *d_a, int *d_deg) {
   ZK_CHECK(hipGetLastError());
 }
 int poly_degree(int curve, int n, const uint64_t *a, bool host_io) {
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  return curve == 0 ? poly_degree_t<CfgBN>(dev, n, a, host_io) : poly_degree_t<CfgBLS>(dev, n, a, host_io);
+  return with_fr(curve, [&](Device &dev, auto cfg) { return poly_degree_t<decltype(cfg)>(dev, n, a, host_io); });
 }
 void arr_op(int curve, int op, int n, const uint64_t *a, const uint64_t *b, const uint64_t *c, const uint64_t *kA,
             const uint64_t *kB, uint64_t *tgt, bool host_io) {
   ZK_REQUIRE(op >= 0 && op < ARR_NUM_OPS, "arr_op: unknown operation");
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  if (curve == 0) arr_op_t<CfgBN>(dev, op, n, a, b, c, kA, kB, tgt, host_io);
-  else arr_op_t<CfgBLS>(dev, op, n, a, b, c, kA, kB, tgt, host_io);
+  with_fr(curve, [&](Device &dev, auto cfg) { arr_op_t<decltype(cfg)>(dev, op, n, a, b, c, kA, kB, tgt, host_io); });
 }
 int arr_pred(int curve, int pred, int n, const uint64_t *a, const uint64_t *b, bool host_io) {
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  return curve == 0 ? arr_pred_t<CfgBN>(dev, pred, n, a, b, host_io) : arr_pred_t<CfgBLS>(dev, pred, n, a, b, host_io);
+  return with_fr(curve, [&](Device &dev, auto cfg) { return arr_pred_t<decltype(cfg)>(dev, pred, n, a, b, host_io); });
 }
 void arr_dot(int curve, int n, const uint64_t *a, const uint64_t *b, uint64_t *tgt_host, bool host_io) {
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  if (curve == 0) arr_dot_t<CfgBN>(dev, n, a, b, tgt_host, host_io);
-  else arr_dot_t<CfgBLS>(dev, n, a, b, tgt_host, host_io);
+  with_fr(curve, [&](Device &dev, auto cfg) { arr_dot_t<decltype(cfg)>(dev, n, a, b, tgt_host, host_io); });
 }
 void arr_powers(int curve, int n, const uint64_t *kA, const uint64_t *kB, uint64_t *tgt, bool host_io) {
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  if (curve == 0) arr_powers_t<CfgBN>(dev, n, kA, kB, tgt, host_io);
-  else arr_powers_t<CfgBLS>(dev, n, kA, kB, tgt, host_io);
+  with_fr(curve, [&](Device &dev, auto cfg) { arr_powers_t<decltype(cfg)>(dev, n, kA, kB, tgt, host_io); });
 }
 int poly_div_by_vanishing(int curve, int n1, const uint64_t *src, int expo_n, const uint64_t *eta, int nquot,
                           uint64_t *quot, int nrem, uint64_t *rem, bool host_io) {
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  return curve == 0 ? div_vanishing_t<CfgBN>(dev, n1, src, expo_n, eta, nquot, quot, nrem, rem, host_io)
-                    : div_vanishing_t<CfgBLS>(dev, n1, src, expo_n, eta, nquot, quot, nrem, rem, host_io);
+  return with_fr(curve, [&](Device &dev, auto cfg) {
+    return div_vanishing_t<decltype(cfg)>(dev, n1, src, expo_n, eta, nquot, quot, nrem, rem, host_io);
+  });
 }
 
 }  // namespace zk

@@ -23,9 +23,7 @@
 #include <thread>
 #include <tuple>
 #include <vector>
-#include "zk_field.hpp"
-#include "zk_host.hpp"
-#include "zk_runtime.hpp"
+#include "zk_frcfg.hpp"  // CfgBN / CfgBLS, with_cfg
 #include "zk_ntt.hpp"
 
 namespace zk {
@@ -505,12 +503,6 @@ static void split_digits(int m, std::vector<int> &d) {
   const int base = m / P, extra = m % P;
   for (int p = 0; p < P; p++) d.push_back(base + (p < extra ? 1 : 0));
 }
-
-// a curve's device and host scalar field, and the one curve dispatch: fn(CfgBN{}) for curve 0, fn(CfgBLS{}) otherwise
-struct CfgBN { using Fd = BN_Fr; using Fh = zkh::BN_Fr; static constexpr int curve = 0; };
-struct CfgBLS { using Fd = BLS_Fr; using Fh = zkh::BLS_Fr; static constexpr int curve = 1; };
-template <class Fn>
-static void with_cfg(int curve, Fn fn) { curve == 0 ? fn(CfgBN{}) : fn(CfgBLS{}); }
 
 // cached twiddle set for one (curve, m, gen, direction)
 struct TwSet {

@@ -24,9 +24,11 @@
 // and the reduced value is < (6 * p * 2p + R' p) / R' = p (1 + 12 p / R') <= 1.19 p < 2p since
 // R' / p >= 2^261 / 2^255 = 64.  tools/poly_bounds.py replays the reduction on the all-(r - 1)
 // operand with Python integers; tests/test_poly_cpu.py runs it.
-#include "zk_field.hpp"
-#include "zk_host.hpp"
-#include "zk_runtime.hpp"
+//
+// Shared with zk_arr.hip: the row helpers, block_sum and k_dot_final (zk_frdev.hpp),
+// CfgBN / CfgBLS, with_fr, ceil_log2 and PowSplit (zk_frcfg.hpp), Stage and read_back (zk_runtime.hpp).
+#include "zk_frdev.hpp"
+#include "zk_frcfg.hpp"
 #include "zk_arr.hpp"
 #include "zk_ntt.hpp"
 #include "zk_poly.hpp"
@@ -35,35 +37,6 @@
 namespace zk {
 
 namespace {
-
-struct U256 {
-  uint64_t w[4];
-};
-
-template <class F>
-__device__ __forceinline__ void ld(Fe<F> &x, const uint64_t *p, size_t i) { fe_load_ref(x, p + i * 4); }
-template <class F>
-__device__ __forceinline__ void st(uint64_t *p, size_t i, const Fe<F> &x) { fe_store_ref(p + i * 4, x); }
-template <class F>
-__device__ __forceinline__ void ld_const(Fe<F> &x, const U256 &k) {
-  uint32_t w[8];
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    w[2 * j] = (uint32_t)k.w[j];
-    w[2 * j + 1] = (uint32_t)(k.w[j] >> 32);
-  }
-  fe_unpack(x, w);
-}
-template <class F>
-__device__ __forceinline__ void lds_get(Fe<F> &x, const uint32_t *p) {
-#pragma unroll
-  for (int q = 0; q < F::N; q++) x.v[q] = p[q];
-}
-template <class F>
-__device__ __forceinline__ void lds_put(uint32_t *p, const Fe<F> &x) {
-#pragma unroll
-  for (int q = 0; q < F::N; q++) p[q] = x.v[q];
-}
 
 constexpr int LAZY_J = 6;  // products per reduction (the bound in the header comment)
 // T += the product-scanning columns of a * b
@@ -152,23 +125,6 @@ __global__ void __launch_bounds__(256) k_poly_pad2(size_t N, size_t n1, const ui
 
 // ---------------------------------------------------------------------------- evaluation
 
-// Block sum of one value per thread (256 threads), the LDS tree of k_dot: thread 0 holds the sum
-template <class F>
-__device__ __forceinline__ void block_sum(Fe<F> &acc, uint32_t *lds) {
-  lds_put(lds + threadIdx.x * F::N, acc);
-  __syncthreads();
-  for (int s = 128; s >= 1; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      Fe<F> o, r;
-      lds_get(o, lds + (threadIdx.x + s) * F::N);
-      fe_add(r, acc, o);
-      acc = r;
-      lds_put(lds + threadIdx.x * F::N, acc);
-    }
-    __syncthreads();
-  }
-}
-
 // x^e (internal form) by square and multiply, e < 2^31
 template <class F>
 __device__ __forceinline__ void fe_pow_u32(Fe<F> &r, const Fe<F> &x, uint32_t e) {
@@ -248,21 +204,7 @@ __global__ void __launch_bounds__(256) k_poly_eval(int n, int T, int h, const ui
   block_sum(acc, lds);
   if (threadIdx.x == 0) st(part, blockIdx.x, acc);
 }
-template <class F>
-__global__ void __launch_bounds__(256) k_poly_eval_final(int nparts, const uint64_t *__restrict__ part,
-                                                         uint64_t *__restrict__ out) {
-  __shared__ uint32_t lds[256 * F::N];
-  Fe<F> acc;
-  fe_zero(acc);
-  for (int i = threadIdx.x; i < nparts; i += 256) {
-    Fe<F> x, s;
-    ld(x, part, i);
-    fe_add(s, acc, x);
-    acc = s;
-  }
-  block_sum(acc, lds);
-  if (threadIdx.x == 0) st(out, 0, acc);
-}
+// the partials are in reference form already: their sum is k_dot_final<F, false> (zk_frdev.hpp)
 
 // ---------------------------------------------------------------------------- linear combination
 
@@ -524,19 +466,28 @@ __global__ void __launch_bounds__(256) k_div_rem(size_t n, const uint64_t *__res
 
 // ---------------------------------------------------------------------------- host side
 
-struct CfgBN { using Fd = BN_Fr; using Fh = zkh::BN_Fr; };
-struct CfgBLS { using Fd = BLS_Fr; using Fh = zkh::BLS_Fr; };
-
 U256 load_u256(const uint64_t *p) {
   U256 u;
   for (int j = 0; j < 4; j++) u.w[j] = p[j];
   return u;
 }
-int ceil_log2(size_t n) {
-  int lg = 0;
-  while (((size_t)1 << lg) < n) lg++;
-  return lg;
-}
+// The transforms of one length 2^lg on device buffers, enqueued on dev.stream: the generator (the
+// table of zkg_fft_generator, fetched once; an inverse transform inverts it itself) and the NTT's
+// scratch of 2^lg rows
+struct Xform {
+  Device &dev;
+  int curve, lg;
+  uint64_t *scratch;
+  uint64_t gen[4];
+  Xform(Device &d, int c, int l, uint64_t *scr) : dev(d), curve(c), lg(l), scratch(scr) {
+    zkg_fft_generator(curve, lg, gen);
+  }
+  void fwd(const uint64_t *src, uint64_t *dst) const { ntt_enqueue(dev, curve, lg, gen, src, dst, scratch, false); }
+  void inv(const uint64_t *src, uint64_t *dst) const { ntt_enqueue(dev, curve, lg, gen, src, dst, scratch, true); }
+  void mul(const uint64_t *a, const uint64_t *b, uint64_t *dst) const {  // pointwise, 2^lg rows
+    arr_mul_enqueue(dev, curve, (size_t)1 << lg, a, b, dst);
+  }
+};
 
 // Shorter factor <= this: the direct kernel.  Measured (profiles/r08a_poly_crossover.txt, short
 // length 1, 2, 4, ... 256 against 2^12, 2^16 and 2^20 long coefficients): the direct kernel wins up
@@ -568,45 +519,31 @@ int poly_mul_t(Device &dev, int curve, int n1, const uint64_t *a, int n2, const 
   const int direct_max = dm < 0 ? POLY_MUL_DIRECT_MAX : dm;
   const bool swap = n2 > n1;  // l: the longer factor
   const int nl = swap ? n2 : n1, ns = swap ? n1 : n2;
+  Stage sg(dev, host_io);
   if (ns <= direct_max) {
     dev.arena.reserve((host_io ? ((size_t)n1 + n2 + N) * 32 : 0) + (1 << 20));
     dev.arena.reset();
-    const uint64_t *da = a, *db = b;
-    uint64_t *dt = tgt;
-    if (host_io) {
-      uint64_t *xa = dev.arena.take<uint64_t>((size_t)n1 * 4);
-      ZK_CHECK(hipMemcpyAsync(xa, a, (size_t)n1 * 32, hipMemcpyHostToDevice, s));
-      da = db = xa;
-      if (!same) {
-        uint64_t *xb = dev.arena.take<uint64_t>((size_t)n2 * 4);
-        ZK_CHECK(hipMemcpyAsync(xb, b, (size_t)n2 * 32, hipMemcpyHostToDevice, s));
-        db = xb;
-      }
-      dt = dev.arena.take<uint64_t>(N * 4);
-    }
+    const uint64_t *da = sg.in(a, (size_t)n1), *db = same ? da : sg.in(b, (size_t)n2);  // squaring: one upload
+    uint64_t *dt = sg.out(tgt, N);
     hipLaunchKernelGGL(k_poly_mul_direct<F>, dim3(div_up(N, 256)), dim3(256), 0, s, nl, swap ? db : da, ns,
                        swap ? da : db, dt);
     ZK_CHECK(hipGetLastError());
-    if (host_io) copy_to_host(dev, s, tgt, dt, N * 32);
+    sg.back(tgt, dt, N);
     ZK_CHECK(hipStreamSynchronize(s));
     g_last_path.store(0);
     return 0;
   }
   const int m = std::max(ceil_log2(N), POLY_MUL_MIN_LOG);
   const size_t M = (size_t)1 << m;
-  uint64_t gen[4];  // the table of zkg_fft_generator; an inverse transform inverts it itself
-  zkg_fft_generator(curve, m, gen);
   // workspace: x, y (operands, then spectra / product), z (spectrum / result), the NTT's scratch
   dev.arena.reserve(4 * M * 32 + (1 << 20));
   dev.arena.reset();
   uint64_t *x = dev.arena.take<uint64_t>(M * 4);
   uint64_t *y = dev.arena.take<uint64_t>(M * 4);
   uint64_t *z = dev.arena.take<uint64_t>(M * 4);
-  uint64_t *scratch = dev.arena.take<uint64_t>(M * 4);
-  if (host_io) {
-    ZK_CHECK(hipMemcpyAsync(x, a, (size_t)n1 * 32, hipMemcpyHostToDevice, s));
-    if (!same) ZK_CHECK(hipMemcpyAsync(y, b, (size_t)n2 * 32, hipMemcpyHostToDevice, s));
-  }
+  const Xform t(dev, curve, m, dev.arena.take<uint64_t>(M * 4));
+  sg.into(x, a, (size_t)n1);  // host rows go straight into the transform buffers
+  if (!same) sg.into(y, b, (size_t)n2);
   {
     const size_t chunks = (same ? 1 : 2) * M * 2;
     const unsigned grid = (unsigned)std::min<size_t>((chunks + 255) / 256, 8192);
@@ -614,15 +551,15 @@ int poly_mul_t(Device &dev, int curve, int n1, const uint64_t *a, int n2, const 
                        (size_t)n2, host_io ? nullptr : b, same ? nullptr : y);
     ZK_CHECK(hipGetLastError());
   }
-  ntt_enqueue(dev, curve, m, gen, x, z, scratch, false);  // z = NTT(a)
+  t.fwd(x, z);  // z = NTT(a)
   if (same) {
-    arr_mul_enqueue(dev, curve, M, z, z, y);  // y = z^2
+    t.mul(z, z, y);  // y = z^2
   } else {
-    ntt_enqueue(dev, curve, m, gen, y, x, scratch, false);  // x = NTT(b)
-    arr_mul_enqueue(dev, curve, M, z, x, y);                // y = z x
+    t.fwd(y, x);     // x = NTT(b)
+    t.mul(z, x, y);  // y = z x
   }
-  ntt_enqueue(dev, curve, m, gen, y, z, scratch, true);  // z = a b, zero above N
-  if (host_io) copy_to_host(dev, s, tgt, z, N * 32);
+  t.inv(y, z);  // z = a b, zero above N
+  if (host_io) sg.back(tgt, z, N);
   else ZK_CHECK(hipMemcpyAsync(tgt, z, N * 32, hipMemcpyDeviceToDevice, s));  // the truncating copy
   ZK_CHECK(hipStreamSynchronize(s));
   g_last_path.store(m);
@@ -642,33 +579,24 @@ void poly_eval_t(Device &dev, int n, const uint64_t *poly, const uint64_t *x, ui
   // SIMD); a short input gets one block, not a grid of empty chains
   size_t T = ((N + 7) / 8 + 255) & ~(size_t)255;
   if (T > ((size_t)1 << 18)) T = (size_t)1 << 18;
-  const int lg = ceil_log2(T), h = (lg + 1) / 2;
-  const int nlo = 1 << h, nhi = (int)((T + nlo - 1) >> h);
+  const PowSplit ps(T);
   const int blocks = (int)(T / 256);
-  dev.arena.reserve((host_io ? N * 32 : 0) + ((size_t)nlo + nhi + blocks + 2) * 256 + (1 << 20));
+  dev.arena.reserve((host_io ? N * 32 : 0) + ((size_t)ps.nlo + ps.nhi + blocks + 2) * 256 + (1 << 20));
   dev.arena.reset();
-  const uint64_t *dp = poly;
-  if (host_io) {
-    uint64_t *d = dev.arena.take<uint64_t>(N * 4);
-    ZK_CHECK(hipMemcpyAsync(d, poly, N * 32, hipMemcpyHostToDevice, s));
-    dp = d;
-  }
-  uint64_t *tlo = dev.arena.take<uint64_t>((size_t)nlo * 4);
-  uint64_t *thi = dev.arena.take<uint64_t>((size_t)nhi * 4);
+  const uint64_t *dp = Stage(dev, host_io).in(poly, N);
+  uint64_t *tlo = dev.arena.take<uint64_t>((size_t)ps.nlo * 4);
+  uint64_t *thi = dev.arena.take<uint64_t>((size_t)ps.nhi * 4);
   uint64_t *ypow = dev.arena.take<uint64_t>(4);
   uint64_t *part = dev.arena.take<uint64_t>((size_t)blocks * 4);
   uint64_t *out = dev.arena.take<uint64_t>(4);
-  hipLaunchKernelGGL(k_poly_eval_tables<F>, dim3(div_up(std::max(nlo, nhi), 256)), dim3(256), 0, s, h, nlo, nhi,
-                     (uint32_t)T, load_u256(x), tlo, thi, ypow);
+  hipLaunchKernelGGL(k_poly_eval_tables<F>, dim3(div_up(std::max(ps.nlo, ps.nhi), 256)), dim3(256), 0, s, ps.h, ps.nlo,
+                     ps.nhi, (uint32_t)T, load_u256(x), tlo, thi, ypow);
   ZK_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_poly_eval<F>, dim3(blocks), dim3(256), 0, s, n, (int)T, h, dp, tlo, thi, ypow, part);
+  hipLaunchKernelGGL(k_poly_eval<F>, dim3(blocks), dim3(256), 0, s, n, (int)T, ps.h, dp, tlo, thi, ypow, part);
   ZK_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_poly_eval_final<F>, dim3(1), dim3(256), 0, s, blocks, part, out);
+  hipLaunchKernelGGL((k_dot_final<F, false>), dim3(1), dim3(DOT_THREADS), 0, s, blocks, part, out);
   ZK_CHECK(hipGetLastError());
-  uint64_t *hres = reinterpret_cast<uint64_t *>(dev.host_staging(32));
-  ZK_CHECK(hipMemcpyAsync(hres, out, 32, hipMemcpyDeviceToHost, s));
-  ZK_CHECK(hipStreamSynchronize(s));
-  memcpy(tgt_host, hres, 32);
+  memcpy(tgt_host, read_back(dev, out, 4), 32);
 }
 
 template <class Cfg>
@@ -690,24 +618,20 @@ void poly_lincomb_t(Device &dev, int K, const int *ns, const uint64_t *coeffs, c
   char *hst = reinterpret_cast<char *>(dev.host_staging(tab));
   LcRow *hrows = reinterpret_cast<LcRow *>(hst + (size_t)K * 32);
   memcpy(hst, coeffs, (size_t)K * 32);
+  Stage sg(dev, host_io);
   for (int k = 0; k < K; k++) {
     const size_t nk = ns[k] > 0 ? (size_t)ns[k] : 0;
     hrows[k].n = (int)nk;
-    hrows[k].p = polys[k];
-    if (host_io && nk) {
-      uint64_t *d = dev.arena.take<uint64_t>(nk * 4);
-      ZK_CHECK(hipMemcpyAsync(d, polys[k], nk * 32, hipMemcpyHostToDevice, s));
-      hrows[k].p = d;
-    }
+    hrows[k].p = nk ? sg.in(polys[k], nk) : polys[k];
   }
-  uint64_t *dt = host_io ? dev.arena.take<uint64_t>(N * 4) : tgt;
+  uint64_t *dt = sg.out(tgt, N);
   char *dtab = dev.arena.take<char>(tab);
   ZK_CHECK(hipMemcpyAsync(dtab, hst, tab, hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_poly_lincomb<F>, dim3(div_up(N, 256)), dim3(256), 0, s, K, (int)N,
                      reinterpret_cast<const LcRow *>(dtab + (size_t)K * 32),
                      reinterpret_cast<const uint64_t *>(dtab), dt);
   ZK_CHECK(hipGetLastError());
-  if (host_io) copy_to_host(dev, s, tgt, dt, N * 32);
+  sg.back(tgt, dt, N);
   ZK_CHECK(hipStreamSynchronize(s));
 }
 
@@ -759,14 +683,12 @@ unsigned copy_grid(size_t items) { return (unsigned)std::min<size_t>((items + 25
 struct DivBufs {
   uint64_t *x, *y, *fx, *fg, *z, *scratch;
 };
-// fx = NTT(x), fg = NTT(y), x = the cyclic product of length 2^lg of what x and y held
-void div_cyclic_product(Device &dev, int curve, int lg, const DivBufs &b) {
-  uint64_t gen[4];
-  zkg_fft_generator(curve, lg, gen);
-  ntt_enqueue(dev, curve, lg, gen, b.x, b.fx, b.scratch, false);
-  ntt_enqueue(dev, curve, lg, gen, b.y, b.fg, b.scratch, false);
-  arr_mul_enqueue(dev, curve, (size_t)1 << lg, b.fx, b.fg, b.z);
-  ntt_enqueue(dev, curve, lg, gen, b.z, b.x, b.scratch, true);
+// fx = NTT(x), fg = NTT(y), x = the cyclic product of t's length of what x and y held
+void div_cyclic_product(const Xform &t, const DivBufs &b) {
+  t.fwd(b.x, b.fx);
+  t.fwd(b.y, b.fg);
+  t.mul(b.fx, b.fg, b.z);
+  t.inv(b.z, b.x);
 }
 // rows of the first fold pass of a source of len rows down to N (0: one pass is enough)
 size_t fold_first(size_t len, size_t N) {
@@ -805,9 +727,7 @@ int poly_div_t(Device &dev, int curve, int n1, const uint64_t *p, int n2, const 
     int *ddeg = dev.arena.take<int>(2);
     poly_degree_enqueue(dev, n1, p, ddeg);
     poly_degree_enqueue(dev, n2, d, ddeg + 1);
-    int *hdeg = reinterpret_cast<int *>(dev.host_staging(8));
-    ZK_CHECK(hipMemcpyAsync(hdeg, ddeg, 8, hipMemcpyDeviceToHost, s));
-    ZK_CHECK(hipStreamSynchronize(s));
+    const int *hdeg = read_back(dev, ddeg, 2);
     dp = hdeg[0];
     dq = hdeg[1];
   }
@@ -849,14 +769,8 @@ int poly_div_t(Device &dev, int curve, int n1, const uint64_t *p, int n2, const 
   dev.arena.reserve((6 * NB + M + (own_q ? M : 0) +
                      (host_io ? (size_t)dp + 1 + (size_t)dq + 1 + (want_rem ? (size_t)dq : 0) : 0)) * 32 + (1 << 20));
   dev.arena.reset();
-  const uint64_t *dpl = p, *ddv = d;
-  if (host_io) {
-    uint64_t *a = dev.arena.take<uint64_t>(((size_t)dp + 1) * 4), *b = dev.arena.take<uint64_t>(((size_t)dq + 1) * 4);
-    ZK_CHECK(hipMemcpyAsync(a, p, ((size_t)dp + 1) * 32, hipMemcpyHostToDevice, s));
-    ZK_CHECK(hipMemcpyAsync(b, d, ((size_t)dq + 1) * 32, hipMemcpyHostToDevice, s));
-    dpl = a;
-    ddv = b;
-  }
+  Stage sg(dev, host_io);
+  const uint64_t *dpl = sg.in(p, (size_t)dp + 1), *ddv = sg.in(d, (size_t)dq + 1);  // the rows up to each degree
   DivBufs B;
   B.x = dev.arena.take<uint64_t>(NB * 4);
   B.y = dev.arena.take<uint64_t>(NB * 4);
@@ -866,7 +780,7 @@ int poly_div_t(Device &dev, int curve, int n1, const uint64_t *p, int n2, const 
   B.scratch = dev.arena.take<uint64_t>(NB * 4);
   uint64_t *g = dev.arena.take<uint64_t>(M * 4);
   uint64_t *dqo = own_q ? dev.arena.take<uint64_t>(M * 4) : quot;
-  uint64_t *dro = !want_rem ? nullptr : host_io ? dev.arena.take<uint64_t>((size_t)dq * 4) : rem;
+  uint64_t *dro = want_rem ? sg.out(rem, (size_t)dq) : nullptr;
 
   const bool prof = g_div_profile.load() != 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -883,18 +797,17 @@ int poly_div_t(Device &dev, int curve, int n1, const uint64_t *p, int n2, const 
   for (int i = 1; i <= steps; i++) {
     const int kn = prec[i], lg = std::max(ceil_log2((size_t)kn), POLY_MUL_MIN_LOG);
     const size_t N = (size_t)1 << lg;
+    const Xform t(dev, curve, lg, B.scratch);
     hipLaunchKernelGGL(k_div_rev_pad2, dim3(copy_grid(4 * N)), dim3(256), 0, s, N, (size_t)std::min(kn, kf), ddv,
                        (size_t)dq, B.x, (size_t)k, g, B.y);
     ZK_CHECK(hipGetLastError());
-    div_cyclic_product(dev, curve, lg, B);  // x = f_{<k'} g_{<k} mod x^N - 1, fg = NTT(g_{<k})
+    div_cyclic_product(t, B);  // x = f_{<k'} g_{<k} mod x^N - 1, fg = NTT(g_{<k})
     hipLaunchKernelGGL(k_div_neg_shift_pad<F>, dim3(copy_grid(N)), dim3(256), 0, s, N, B.x, (size_t)k,
                        (size_t)(kn - k), B.y);
     ZK_CHECK(hipGetLastError());
-    uint64_t gen[4];
-    zkg_fft_generator(curve, lg, gen);
-    ntt_enqueue(dev, curve, lg, gen, B.y, B.fx, B.scratch, false);
-    arr_mul_enqueue(dev, curve, N, B.fx, B.fg, B.z);
-    ntt_enqueue(dev, curve, lg, gen, B.z, B.x, B.scratch, true);  // x[0, k' - k) = g[k, k')
+    t.fwd(B.y, B.fx);
+    t.mul(B.fx, B.fg, B.z);
+    t.inv(B.z, B.x);  // x[0, k' - k) = g[k, k')
     ZK_CHECK(hipMemcpyAsync(g + (size_t)k * 4, B.x, (size_t)(kn - k) * 32, hipMemcpyDeviceToDevice, s));
     k = kn;
   }
@@ -907,7 +820,7 @@ int poly_div_t(Device &dev, int curve, int n1, const uint64_t *p, int n2, const 
     const size_t N = (size_t)1 << lgq;
     hipLaunchKernelGGL(k_div_rev_pad2, dim3(copy_grid(4 * N)), dim3(256), 0, s, N, M, dpl, (size_t)dp, B.x, M, g, B.y);
     ZK_CHECK(hipGetLastError());
-    div_cyclic_product(dev, curve, lgq, B);  // 2m - 1 <= N: nothing wraps
+    div_cyclic_product(Xform(dev, curve, lgq, B.scratch), B);  // 2m - 1 <= N: nothing wraps
     hipLaunchKernelGGL(k_div_rev_trunc, dim3(copy_grid(2 * M)), dim3(256), 0, s, M, B.x, dqo);
     ZK_CHECK(hipGetLastError());
   }
@@ -918,13 +831,12 @@ int poly_div_t(Device &dev, int curve, int n1, const uint64_t *p, int n2, const 
     div_fold<F>(s, dpl, (size_t)dp + 1, N, B.z, B.fx, B.fg);
     div_fold<F>(s, dqo, M, N, B.x, B.fx, B.fg);
     div_fold<F>(s, ddv, (size_t)dq + 1, N, B.y, B.fx, B.fg);
-    uint64_t gen[4];
-    zkg_fft_generator(curve, lgr, gen);
+    const Xform t(dev, curve, lgr, B.scratch);
     // fold(p) stays in z: the pointwise product goes back into x and the inverse transform into y
-    ntt_enqueue(dev, curve, lgr, gen, B.x, B.fx, B.scratch, false);
-    ntt_enqueue(dev, curve, lgr, gen, B.y, B.fg, B.scratch, false);
-    arr_mul_enqueue(dev, curve, N, B.fx, B.fg, B.x);
-    ntt_enqueue(dev, curve, lgr, gen, B.x, B.y, B.scratch, true);
+    t.fwd(B.x, B.fx);
+    t.fwd(B.y, B.fg);
+    t.mul(B.fx, B.fg, B.x);
+    t.inv(B.x, B.y);
     hipLaunchKernelGGL(k_div_rem<F>, dim3(copy_grid((size_t)dq)), dim3(256), 0, s, (size_t)dq, B.z, B.y, dro);
     ZK_CHECK(hipGetLastError());
   }
@@ -932,10 +844,8 @@ int poly_div_t(Device &dev, int curve, int n1, const uint64_t *p, int n2, const 
   // ---- write-out: the tails are zero (poly_mont.c:273-274)
   zero_rows(quot, M, (size_t)nquot);
   zero_rows(rem, (size_t)dq, (size_t)nrem);
-  if (host_io) {
-    if (quot) copy_to_host(dev, s, quot, dqo, M * 32);
-    if (want_rem) copy_to_host(dev, s, rem, dro, (size_t)dq * 32);
-  }
+  if (quot) sg.back(quot, dqo, M);
+  if (want_rem) sg.back(rem, dro, (size_t)dq);
   ZK_CHECK(hipStreamSynchronize(s));
   if (prof) {
     float ms[3];
@@ -954,23 +864,16 @@ int poly_div_t(Device &dev, int curve, int n1, const uint64_t *p, int n2, const 
 
 int poly_mul(int curve, int n1, const uint64_t *a, int n2, const uint64_t *b, uint64_t *tgt, bool host_io) {
   ZK_REQUIRE(curve == 0 || curve == 1, "poly_mul: unknown curve");
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  return curve == 0 ? poly_mul_t<CfgBN>(dev, curve, n1, a, n2, b, tgt, host_io)
-                    : poly_mul_t<CfgBLS>(dev, curve, n1, a, n2, b, tgt, host_io);
+  return with_fr(curve, [&](Device &dev, auto cfg) {
+    return poly_mul_t<decltype(cfg)>(dev, curve, n1, a, n2, b, tgt, host_io);
+  });
 }
 void poly_eval(int curve, int n, const uint64_t *poly, const uint64_t *x, uint64_t *tgt_host, bool host_io) {
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  if (curve == 0) poly_eval_t<CfgBN>(dev, n, poly, x, tgt_host, host_io);
-  else poly_eval_t<CfgBLS>(dev, n, poly, x, tgt_host, host_io);
+  with_fr(curve, [&](Device &dev, auto cfg) { poly_eval_t<decltype(cfg)>(dev, n, poly, x, tgt_host, host_io); });
 }
 void poly_lincomb(int curve, int K, const int *ns, const uint64_t *coeffs, const uint64_t *const *polys,
                   uint64_t *tgt, bool host_io) {
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  if (curve == 0) poly_lincomb_t<CfgBN>(dev, K, ns, coeffs, polys, tgt, host_io);
-  else poly_lincomb_t<CfgBLS>(dev, K, ns, coeffs, polys, tgt, host_io);
+  with_fr(curve, [&](Device &dev, auto cfg) { poly_lincomb_t<decltype(cfg)>(dev, K, ns, coeffs, polys, tgt, host_io); });
 }
 int poly_long_div(int curve, int n1, const uint64_t *p, int n2, const uint64_t *d, int nquot, uint64_t *quot, int nrem,
                   uint64_t *rem, bool host_io) {
@@ -979,10 +882,9 @@ int poly_long_div(int curve, int n1, const uint64_t *p, int n2, const uint64_t *
   if (curve != 0 && curve != 1) return -1;
   if (n1 < 0 || n2 < 0 || (quot && nquot < 0) || (rem && nrem < 0)) return -1;
   if (n1 > (1 << (POLY_MUL_MAX_LOG[curve] - 1))) return -1;
-  Device &dev = current_device();
-  std::lock_guard<std::mutex> lock(dev.mu);
-  return curve == 0 ? poly_div_t<CfgBN>(dev, curve, n1, p, n2, d, nquot, quot, nrem, rem, host_io)
-                    : poly_div_t<CfgBLS>(dev, curve, n1, p, n2, d, nquot, quot, nrem, rem, host_io);
+  return with_fr(curve, [&](Device &dev, auto cfg) {
+    return poly_div_t<decltype(cfg)>(dev, curve, n1, p, n2, d, nquot, quot, nrem, rem, host_io);
+  });
 }
 void poly_set_div_base_max(int len) { g_div_base.store(len < 0 ? -1 : len); }
 int poly_div_base_max() { return div_base_in_force(); }

@@ -268,4 +268,34 @@ struct StagedIO {
   }
 };
 
+// Host operands of the Fr units, in rows of 4 x u64 (same rules as StagedIO; several inputs and
+// outputs per call): every host array is copied into the call's arena, a device pointer passes through
+struct Stage {
+  Device &dev;
+  bool host;
+  explicit Stage(Device &d, bool h) : dev(d), host(h) {}
+  void into(uint64_t *d, const uint64_t *p, size_t n) {  // the upload alone, into rows the caller took
+    if (host && n) ZK_CHECK(hipMemcpyAsync(d, p, n * 32, hipMemcpyHostToDevice, dev.stream));
+  }
+  const uint64_t *in(const uint64_t *p, size_t n) {
+    if (!host || !p) return p;
+    uint64_t *d = dev.arena.take<uint64_t>(n * 4);
+    into(d, p, n);
+    return d;
+  }
+  uint64_t *out(uint64_t *p, size_t n) { return host ? dev.arena.take<uint64_t>(n * 4) : p; }
+  void back(uint64_t *host_p, const uint64_t *dev_p, size_t n) {  // waits (pinned pieces for large outputs)
+    if (host && n) copy_to_host(dev, dev.stream, host_p, dev_p, n * 32);
+  }
+};
+// `count` values of device memory through the pinned staging, after everything enqueued on
+// dev.stream: waits, and the result is good until the context's staging is used again
+template <class T>
+inline const T *read_back(Device &dev, const T *d_ptr, size_t count = 1) {
+  T *h = reinterpret_cast<T *>(dev.host_staging(count * sizeof(T)));
+  ZK_CHECK(hipMemcpyAsync(h, d_ptr, count * sizeof(T), hipMemcpyDeviceToHost, dev.stream));
+  ZK_CHECK(hipStreamSynchronize(dev.stream));
+  return h;
+}
+
 }  // namespace zk
