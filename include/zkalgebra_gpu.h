@@ -445,6 +445,51 @@ ZKG_API void zkg_g2_fft_device(int curve, int inverse, int m, const uint64_t *ge
  * so that the grid-stride loop of a stage is exercised at small sizes */
 ZKG_API void zkg_g2_fft_set_max_lanes(int lanes);
 
+/* Batch G1 scalar multiplication (the reference's <C>_G1_proj_scl_Fr_mont / _scl_Fr_std, G1_proj.c:462-489,
+ * followed by _normalize or _to_affine, once per row).
+ *   fixed:  tgt[i] = [k_i] P     one affine base P (HOST, 2 NP words, all-0xFF = infinity) and n scalars
+ *   rows:   tgt[i] = [k_i] P_i   n affine bases (all-0xFF rows stay infinity)
+ *   powers: tgt[i] = [a tau^i] P a, tau one Montgomery Fr each (HOST; a NULL = 1): the KZG `taus`
+ * Scalars are rows of 4 words: expos_mont = 1 Montgomery Fr, brought to canonical standard form first;
+ * expos_mont = 0 raw 256-bit integers used verbatim (values >= r, up to 2^256 - 1, included).  The
+ * multiplication is by the integer, so the result equals the reference's for every on-curve base, also
+ * outside the order-r subgroup.  That includes the one place where the reference's row is not the group's:
+ * for a base of order 3 (x = 0: (0, +-2) on BLS12-381; BN128 has none) its 4-bit table holds the double of
+ * infinity as (0 : 0 : 0), which absorbs every sum, so a scalar with a hexadecimal digit 6, 7 or c .. f gives
+ * infinity there and here, whatever k mod 3 is (DESIGN.md "Batch scalar multiplication").  Target rows: affine_out = 0 normalised projective (x : y : 1), infinity
+ * (0 : 1 : 0), 3 NP words; affine_out = 1 affine (x, y), infinity all-0xFF, 2 NP words.
+ * Returns 0, or -1 with nothing written for n < 0 or a curve that is neither ZKG_BN128 nor ZKG_BLS12_381.
+ * n == 0 is a no-op.  Outputs alias no input; nothing outside rows [0, n) of the target is written.
+ * Synchronous and thread-safe, on the calling thread's device; device errors go through the error
+ * channel (zkg_set_error_mode / zkg_last_error). */
+ZKG_API int zkg_g1_scl_fixed_device(int curve, int n, const uint64_t *d_expos, int expos_mont,
+                                    const uint64_t *base_affine, int affine_out, uint64_t *d_tgt);  /* DEVICE expos, tgt */
+ZKG_API int zkg_g1_scl_fixed(int curve, int n, const uint64_t *expos, int expos_mont, const uint64_t *base_affine,
+                             int affine_out, uint64_t *tgt);                                        /* HOST pointers */
+ZKG_API int zkg_g1_scl_rows_device(int curve, int n, const uint64_t *d_expos, int expos_mont, const uint64_t *d_bases,
+                                   int affine_out, uint64_t *d_tgt);                                /* DEVICE pointers */
+ZKG_API int zkg_g1_scl_rows(int curve, int n, const uint64_t *expos, int expos_mont, const uint64_t *bases,
+                            int affine_out, uint64_t *tgt);                                         /* HOST pointers */
+ZKG_API int zkg_g1_scl_powers_device(int curve, int n, const uint64_t *a, const uint64_t *tau,
+                                     const uint64_t *base_affine, int affine_out, uint64_t *d_tgt); /* DEVICE tgt */
+ZKG_API int zkg_g1_scl_powers(int curve, int n, const uint64_t *a, const uint64_t *tau, const uint64_t *base_affine,
+                              int affine_out, uint64_t *tgt);                                       /* HOST tgt */
+/* test hooks.  set_window: the window c of the fixed-base table (0 restores the default; other values
+ * are clamped to 2..16).  set_fixed_min: fixed-base and powers calls below n rows take the per-row
+ * kernel instead of building the table (< 0: the default, 0: never).  last_path: 0 when the most recent
+ * fixed-base or powers call ran the per-row kernel (or built no table: base at infinity), else the
+ * window its table path ran with.  The results do not depend on either setting. */
+ZKG_API void zkg_g1_scl_set_window(int c);
+ZKG_API void zkg_g1_scl_set_fixed_min(int n);
+ZKG_API int  zkg_g1_scl_last_path(void);
+/* the signed-window recoding of the fixed-base kernel (no GPU call): digits[w], w < W = ceil(257 / c), of
+ * the 256-bit integer k with sum_w digits[w] 2^(c w) = k and |digits[w]| <= 2^(c - 1); at most cap
+ * entries are written.  Returns W, or -1 for c outside 2..16. */
+ZKG_API int  zkg_g1_scl_digits(int c, const uint64_t k[4], int *digits, int cap);
+/* bytes of the fixed-base table for window c (clamped to 2..16): 2^(c-1) ceil(257 / c) rows of 2 NP
+ * words (no GPU call); 0 for an unknown curve */
+ZKG_API size_t zkg_g1_scl_table_bytes(int curve, int c);
+
 /* host helpers on G1 (projective, reference Montgomery form) */
 ZKG_API void zkg_g1_proj_add(int curve, const uint64_t *a, const uint64_t *b, uint64_t *out);
 ZKG_API void zkg_g1_proj_normalize(int curve, const uint64_t *a, uint64_t *out);

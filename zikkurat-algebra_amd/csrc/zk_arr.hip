@@ -900,6 +900,20 @@ static void arr_dot_t(Device &dev, int n, const uint64_t *a, const uint64_t *b, 
   memcpy(tgt_host, read_back(dev, out, 4), 32);
 }
 
+// dt[i] = kA kB^i, i < n (n > 0), enqueued on dev.stream: the two tables come from the call's arena
+// (arr_powers_scratch_bytes inside the caller's reserve)
+template <class F>
+static void powers_launch(Device &dev, int n, const uint64_t *kA, const uint64_t *kB, uint64_t *dt) {
+  const PowSplit ps((size_t)n);
+  uint64_t *tlo = dev.arena.take<uint64_t>((size_t)ps.nlo * 4);
+  uint64_t *thi = dev.arena.take<uint64_t>((size_t)ps.nhi * 4);
+  hipLaunchKernelGGL(k_pow_tables<F>, dim3(div_up(std::max(ps.nlo, ps.nhi), 256)), dim3(256), 0, dev.stream, ps.h,
+                     ps.nlo, ps.nhi, load_u256(kA), load_u256(kB), tlo, thi);
+  ZK_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(k_powers<F>, dim3(stream_grid((size_t)n, true)), dim3(256), 0, dev.stream, n, ps.h, tlo, thi, dt);
+  ZK_CHECK(hipGetLastError());
+}
+
 template <class Cfg>
 static void arr_powers_t(Device &dev, int n, const uint64_t *kA, const uint64_t *kB, uint64_t *tgt, bool host_io) {
   using F = typename Cfg::Fd;
@@ -911,13 +925,7 @@ static void arr_powers_t(Device &dev, int n, const uint64_t *kA, const uint64_t 
   dev.arena.reset();
   Stage sg(dev, host_io);
   uint64_t *dt = sg.out(tgt, N);
-  uint64_t *tlo = dev.arena.take<uint64_t>((size_t)ps.nlo * 4);
-  uint64_t *thi = dev.arena.take<uint64_t>((size_t)ps.nhi * 4);
-  hipLaunchKernelGGL(k_pow_tables<F>, dim3(div_up(std::max(ps.nlo, ps.nhi), 256)), dim3(256), 0, st, ps.h, ps.nlo,
-                     ps.nhi, load_u256(kA), load_u256(kB), tlo, thi);
-  ZK_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_powers<F>, dim3(stream_grid(N, true)), dim3(256), 0, st, n, ps.h, tlo, thi, dt);
-  ZK_CHECK(hipGetLastError());
+  powers_launch<F>(dev, n, kA, kB, dt);
   sg.back(tgt, dt, N);
   ZK_CHECK(hipStreamSynchronize(st));
 }
@@ -1004,6 +1012,14 @@ void arr_mul_enqueue(Device &dev, int curve, size_t n, const uint64_t *d_a, cons
   with_cfg(curve, [&](auto cfg) {
     launch_arr_op<typename decltype(cfg)::Fd>(ARR_MUL, g, dim3(stream_grid(n, true)), dev.stream);
   });
+}
+size_t arr_powers_scratch_bytes(size_t n) {
+  const PowSplit ps(n ? n : 1);
+  return ((size_t)ps.nlo + ps.nhi) * 32 + 512;
+}
+void arr_powers_enqueue(Device &dev, int curve, int n, const uint64_t *kA, const uint64_t *kB, uint64_t *d_tgt) {
+  if (n <= 0) return;
+  with_cfg(curve, [&](auto cfg) { powers_launch<typename decltype(cfg)::Fd>(dev, n, kA, kB, d_tgt); });
 }
 void poly_degree_enqueue(Device &dev, int n, const uint64_t *d_a, int *d_deg) {
   ZK_CHECK(hipMemsetAsync(d_deg, 0xff, 4, dev.stream));  // -1

@@ -49,6 +49,11 @@ struct Device;
 // d_tgt = d_a * d_b element-wise on DEVICE buffers, enqueued on dev.stream without touching the
 // arena and without waiting (caller holds dev.mu; n < 2^31): the pointwise step of zk_poly.hip
 void arr_mul_enqueue(Device &dev, int curve, size_t n, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_tgt);
+// d_tgt[i] = kA kB^i, i < n (kA, kB on the host), the two launches of arr_powers enqueued on dev.stream
+// without resetting the arena and without waiting (caller holds dev.mu): the power tables are taken from
+// the arena, arr_powers_scratch_bytes(n) of it.  The scalars of zk_scl.hip's powers entry.
+size_t arr_powers_scratch_bytes(size_t n);
+void arr_powers_enqueue(Device &dev, int curve, int n, const uint64_t *kA, const uint64_t *kB, uint64_t *d_tgt);
 // *d_deg = degree of the DEVICE array d_a[0, n) (-1: zero or n <= 0), the reduction of poly_degree
 // enqueued on dev.stream without touching the arena and without waiting (caller holds dev.mu): the
 // division of zk_poly.hip finds both of its degrees with one wait

@@ -312,6 +312,59 @@ ZKG_API void zkg_g1_jac_batch_to_affine_device(int curve, int n, const uint64_t 
 
 }  // extern "C"
 
+// ---------------------------------------------------------------------------- G1 batch scalar multiplication
+// a host loop over <C>_G1_proj_scl_Fr_mont / _scl_Fr_std (bls12_381_G1_proj.c:462-489) and normalize / to_affine
+#include "zk_scl.hpp"
+
+namespace {
+bool scl_args_ok(int curve, int n) { return n >= 0 && (curve == ZKG_BN128 || curve == ZKG_BLS12_381); }
+}  // namespace
+
+extern "C" {
+
+#define ZKG_SCL_ENTRY(NAME, FN, HOST_IO)                                                                              \
+  ZKG_API int NAME(int curve, int n, const uint64_t *expos, int expos_mont, const uint64_t *bases, int affine_out,    \
+                   uint64_t *tgt) {                                                                                   \
+    if (!scl_args_ok(curve, n)) return -1;                                                                            \
+    guard([&] { zk::FN(curve, n, expos, expos_mont != 0, bases, affine_out != 0, tgt, HOST_IO); });                   \
+    return 0;                                                                                                         \
+  }
+ZKG_SCL_ENTRY(zkg_g1_scl_fixed_device, g1_scl_fixed, false)
+ZKG_SCL_ENTRY(zkg_g1_scl_fixed, g1_scl_fixed, true)
+ZKG_SCL_ENTRY(zkg_g1_scl_rows_device, g1_scl_rows, false)
+ZKG_SCL_ENTRY(zkg_g1_scl_rows, g1_scl_rows, true)
+
+ZKG_API int zkg_g1_scl_powers_device(int curve, int n, const uint64_t *a, const uint64_t *tau,
+                                     const uint64_t *base_affine, int affine_out, uint64_t *d_tgt) {
+  if (!scl_args_ok(curve, n)) return -1;
+  guard([&] { zk::g1_scl_powers(curve, n, a, tau, base_affine, affine_out != 0, d_tgt, false); });
+  return 0;
+}
+ZKG_API int zkg_g1_scl_powers(int curve, int n, const uint64_t *a, const uint64_t *tau, const uint64_t *base_affine,
+                              int affine_out, uint64_t *tgt) {
+  if (!scl_args_ok(curve, n)) return -1;
+  guard([&] { zk::g1_scl_powers(curve, n, a, tau, base_affine, affine_out != 0, tgt, true); });
+  return 0;
+}
+ZKG_API void zkg_g1_scl_set_window(int c) { zk::g1_scl_set_window(c); }
+ZKG_API void zkg_g1_scl_set_fixed_min(int n) { zk::g1_scl_set_fixed_min(n); }
+ZKG_API int zkg_g1_scl_last_path(void) { return zk::g1_scl_last_path(); }
+ZKG_API int zkg_g1_scl_digits(int c, const uint64_t k[4], int *digits, int cap) {
+  if (c < zk::SCL_WINDOW_MIN || c > zk::SCL_WINDOW_MAX) return -1;
+  const int W = zk::scl_windows(c);
+  int carry = 0;
+  for (int w = 0; w < W; w++) {
+    const int d = zk::scl_digit(k, c, w, carry);
+    if (w < cap) digits[w] = d;
+  }
+  return W;
+}
+ZKG_API size_t zkg_g1_scl_table_bytes(int curve, int c) {
+  return curve == ZKG_BN128 || curve == ZKG_BLS12_381 ? zk::g1_scl_table_bytes(curve, c) : 0;
+}
+
+}  // extern "C"
+
 // ---------------------------------------------------------------------------- G2 batch conversions
 // <C>_G2_proj_batch_from_affine / _batch_to_affine (bls12_381_G2_proj.c:139-158; G2/Proj.hs:386-405)
 #include "zk_g2ext.hpp"

@@ -362,7 +362,10 @@ __device__ __forceinline__ uint32_t win5(const uint64_t *K, int i) {
 #ifndef ZK_FFT_SCL_ATTR
 #define ZK_FFT_SCL_ATTR __forceinline__
 #endif
-template <class F>
+// INF_ROWS: a table entry d P may be the point at infinity (P of an order <= 16: 3 and 11 divide the
+// BLS12-381 G1 cofactor) and is then skipped; jac_add_cached takes finite entries only.  The group FFT's
+// stages are compiled without it, as before; the per-row scalar multiplications (zk_scl.hip) with it.
+template <class F, bool INF_ROWS = false>
 __device__ ZK_FFT_SCL_ATTR void xyzz_scl(Xyzz<F> &r, const Xyzz<F> &P, const uint64_t *k, uint32_t *__restrict__ tab) {
   if (xyzz_is_inf(P)) {
     r = P;
@@ -419,7 +422,7 @@ __device__ ZK_FFT_SCL_ATTR void xyzz_scl(Xyzz<F> &r, const Xyzz<F> &P, const uin
         fe_neg(ny, e.Y);
         e.Y = ny;
       }
-      jac_add_cached(acc, e);
+      if (!INF_ROWS || !fe_is_zero(e.Z)) jac_add_cached(acc, e);
     }
   }
   if (jac_is_inf(acc)) {
@@ -496,5 +499,12 @@ __global__ void __launch_bounds__(256) k_fft_inv_stage(int m, int s, const uint3
 // inverse, e < cnt, 4 u64 each -- the reference's gpow sequences (G1_proj.c:705-711, 758-764; the G2
 // file's are the same), canonical Fr in standard form; gen: the host's Montgomery generator
 void fft_int_twiddles(int curve, hipStream_t st, const uint64_t *gen, bool inverse, size_t cnt, uint64_t *tw);
+
+// the group FFT's closing normalisation on its own, enqueued on st (zk_g1ext.hip, k_norm_chunks): n G1 XYZZ
+// rows `src` (ZZ = 0: infinity) -> rows (x : y : 1) / (0 : 1 : 0) of 3 NP words, or with `affine` rows
+// (x, y) of 2 NP words, all-0xFF at infinity; scratch: n NP words.  The scalar multiplications of
+// zk_scl.hip end with it.
+void g1_norm_xyzz_enqueue(int curve, hipStream_t st, int n, const uint32_t *src, uint64_t *scratch, uint64_t *tgt,
+                          bool affine);
 
 }  // namespace zk

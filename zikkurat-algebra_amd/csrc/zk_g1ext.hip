@@ -86,7 +86,9 @@ __global__ void __launch_bounds__(256) k_from_affine(int n, const uint64_t *__re
 // MODE_XYZZ_TO_PROJ: src = device XYZZ, tgt = normalised reference projective, written at
 //                    index bitrev_m(i) when m >= 0 (inverse FFT output order)
 // MODE_JAC_TO_AFF  : src = reference Jacobian (X:Y:Z), tgt = affine (X/Z^2, Y/Z^3) / 0xFF..
-enum { MODE_PROJ_TO_AFF = 0, MODE_XYZZ_TO_PROJ = 1, MODE_JAC_TO_AFF = 2 };
+// MODE_XYZZ_TO_AFF : src = device XYZZ, tgt = affine (X/ZZ, Y/ZZZ) / 0xFF.. (the scalar multiplications
+//                    of zk_scl.hip)
+enum { MODE_PROJ_TO_AFF = 0, MODE_XYZZ_TO_PROJ = 1, MODE_JAC_TO_AFF = 2, MODE_XYZZ_TO_AFF = 3 };
 
 // Round 6: the chunk of lane t is the strided set {t, t + T, ...} (T = lanes, as k_inv_chunks):
 // neighbouring lanes touch neighbouring point rows.  STRIDED = false: CHK consecutive points.
@@ -109,8 +111,9 @@ __global__ void __launch_bounds__(256) k_norm_chunks(int n, int CHK, const void 
   const size_t cnt = left < (size_t)CHK ? left : (size_t)CHK;
   const uint64_t *srcp = reinterpret_cast<const uint64_t *>(srcv);
   const uint32_t *srcx = reinterpret_cast<const uint32_t *>(srcv);
+  constexpr bool XYZZ_SRC = MODE == MODE_XYZZ_TO_PROJ || MODE == MODE_XYZZ_TO_AFF;
   auto den = [&](size_t i, Fe<F> &d) -> bool {  // denominator (internal); false = infinity
-    if (MODE != MODE_XYZZ_TO_PROJ) {
+    if (!XYZZ_SRC) {
       ld_int(d, srcp + i * 3 * NP + 2 * NP);
     } else {
       fe_load_u(d, srcx + i * xw<F>() + 3 * F::SN);  // ZZZ
@@ -189,10 +192,15 @@ __global__ void __launch_bounds__(256) k_norm_chunks(int n, int CHK, const void 
         fe_sqr(iz2, iz);         // 1/ZZ
         fe_mul(x, p.X, iz2);
         fe_mul(y, p.Y, dinv);
-        uint64_t *qo = tgt + o * 3 * NP;
-        st_ref_or(qo, x, fin, zeros);  // infinity: (0 : 1 : 0)
-        st_ref_or(qo + NP, y, fin, oneref);
-        st_ref_or(qo + 2 * NP, one_int, fin, zeros);
+        if (MODE == MODE_XYZZ_TO_AFF) {
+          st_ref_or(tgt + o * 2 * NP, x, fin, ones);
+          st_ref_or(tgt + o * 2 * NP + NP, y, fin, ones);
+        } else {
+          uint64_t *qo = tgt + o * 3 * NP;
+          st_ref_or(qo, x, fin, zeros);  // infinity: (0 : 1 : 0)
+          st_ref_or(qo + NP, y, fin, oneref);
+          st_ref_or(qo + 2 * NP, one_int, fin, zeros);
+        }
       }
     }
     return;
@@ -246,10 +254,15 @@ __global__ void __launch_bounds__(256) k_norm_chunks(int n, int CHK, const void 
       fe_sqr(iz2, iz);         // 1/ZZ
       fe_mul(x, p.X, iz2);
       fe_mul(y, p.Y, dinv);
-      uint64_t *qo = tgt + o * 3 * NP;
-      st_ref(qo, x);
-      st_ref(qo + NP, y);
-      st_ref(qo + 2 * NP, one_int);
+      if (MODE == MODE_XYZZ_TO_AFF) {
+        st_ref(tgt + o * 2 * NP, x);
+        st_ref(tgt + o * 2 * NP + NP, y);
+      } else {
+        uint64_t *qo = tgt + o * 3 * NP;
+        st_ref(qo, x);
+        st_ref(qo + NP, y);
+        st_ref(qo + 2 * NP, one_int);
+      }
     }
   }
 }
@@ -1307,6 +1320,16 @@ static void g1_fft_t(Device &dev, int m, const uint64_t *gen, const uint64_t *sr
 
 // ---------------------------------------------------------------------------- public
 
+void g1_norm_xyzz_enqueue(int curve, hipStream_t st, int n, const uint32_t *src, uint64_t *scratch, uint64_t *tgt,
+                          bool affine) {
+  if (n <= 0) return;
+  on_curve<BN254, BLS381>(curve, [&](auto c) {
+    using C = decltype(c);
+    const W6 pm2 = exp_p_minus_2<typename HostOf<C>::Fp>();
+    if (affine) launch_norm<C, MODE_XYZZ_TO_AFF>(st, n, norm_chk((size_t)n), src, scratch, tgt, pm2, 0);
+    else launch_norm<C, MODE_XYZZ_TO_PROJ>(st, n, norm_chk((size_t)n), src, scratch, tgt, pm2, 0);
+  });
+}
 void g1_batch_from_affine(int curve, int n, const uint64_t *src, uint64_t *tgt, bool host_io, bool jac) {
   with_g1(curve, [&](Device &dev, auto c) { batch_from_affine_t<decltype(c)>(dev, n, src, tgt, host_io, jac); });
 }

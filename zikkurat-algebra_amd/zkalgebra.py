@@ -85,6 +85,10 @@ EXTENSION_SYMBOLS += ["zkg_poly_long_div_device", "zkg_poly_long_div", "zkg_poly
 EXTENSION_SYMBOLS += ["zkg_ntt_ext_device", "zkg_ntt_ext", "zkg_ntt_ext_set_max_grid"]
 # cache hooks of the NTT twiddle and shift tables
 EXTENSION_SYMBOLS += ["zkg_ntt_set_cache_limit", "zkg_ntt_cache_bytes"]
+# batch G1 scalar multiplication (fixed base, per-row bases, powers of a scalar) and its hooks
+EXTENSION_SYMBOLS += [f"zkg_g1_scl_{k}{d}" for k in ("fixed", "rows", "powers") for d in ("", "_device")] + [
+    "zkg_g1_scl_set_window", "zkg_g1_scl_set_fixed_min", "zkg_g1_scl_last_path", "zkg_g1_scl_digits",
+    "zkg_g1_scl_table_bytes"]
 
 _lib = None
 
@@ -167,6 +171,23 @@ def load():
                                                          ctypes.c_void_p]
         for f in (lib.zkg_g1_batch_to_affine_device, lib.zkg_g1_jac_batch_to_affine_device):
             f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        lib.zkg_g1_fft_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, U64P, ctypes.c_void_p,
+                                          ctypes.c_void_p]
+        if hasattr(lib, "zkg_g1_scl_fixed"):  # absent from an older variant build, as above
+            lib.zkg_g1_scl_fixed_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, U64P,
+                                                    ctypes.c_int, ctypes.c_void_p]
+            lib.zkg_g1_scl_rows_device.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                   ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+            for f in (lib.zkg_g1_scl_fixed, lib.zkg_g1_scl_rows):
+                f.argtypes = [ctypes.c_int, ctypes.c_int, U64P, ctypes.c_int, U64P, ctypes.c_int, U64P]
+            lib.zkg_g1_scl_powers_device.argtypes = [ctypes.c_int, ctypes.c_int, U64P, U64P, U64P, ctypes.c_int,
+                                                     ctypes.c_void_p]
+            lib.zkg_g1_scl_powers.argtypes = [ctypes.c_int, ctypes.c_int, U64P, U64P, U64P, ctypes.c_int, U64P]
+            lib.zkg_g1_scl_set_window.argtypes = [ctypes.c_int]
+            lib.zkg_g1_scl_set_fixed_min.argtypes = [ctypes.c_int]
+            lib.zkg_g1_scl_digits.argtypes = [ctypes.c_int, U64P, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+            lib.zkg_g1_scl_table_bytes.restype = ctypes.c_size_t
+            lib.zkg_g1_scl_table_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
         lib.zkg_last_error.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         lib.zkg_comm_unique_id.argtypes = [ctypes.c_void_p]
         lib.zkg_comm_init.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
@@ -976,6 +997,147 @@ def batch_to_affine_device(curve, n, d_src, d_tgt, coords="proj"):
     of 3 NP words -> n rows of 2 NP words; distinct buffers"""
     f = load().zkg_g1_batch_to_affine_device if _coords(coords) == "proj" else load().zkg_g1_jac_batch_to_affine_device
     f(CURVE_ID[curve], n, d_src.ptr, d_tgt.ptr)
+
+
+def g1_fft_device(curve, m, gen, d_src, d_dst, inverse=False):
+    """device-resident G1 group FFT: d_src / d_dst are DeviceBuffers of 2^m projective rows"""
+    load().zkg_g1_fft_device(CURVE_ID[curve], 1 if inverse else 0, m, _p(np.ascontiguousarray(gen, dtype=np.uint64)),
+                             d_src.ptr, d_dst.ptr)
+
+
+# ----------------------------------------------------------------------------- batch scalar multiplication
+
+def _scl_rc(rc, name):
+    if rc != 0:
+        raise ValueError(f"{name}: negative length or unknown curve")
+
+
+def _g1_aff(curve, base, name):
+    base = np.ascontiguousarray(base, dtype=np.uint64).reshape(-1)
+    if base.shape[0] != 2 * NLIMBS_P[curve]:
+        raise ValueError(f"{name}: the base must be one affine G1 point (x, y) in Montgomery form")
+    return base
+
+
+def _scl_out(curve, n, affine):
+    return np.zeros((n, (2 if affine else 3) * NLIMBS_P[curve]), dtype=np.uint64)
+
+
+def scalar_mul_fixed(curve, scalars, base, std=False, affine=False):
+    """[k_i] P for one affine base P: map (`scalarMul` p) over a FlatArray of scalars (scl_Fr_mont, or
+    scl_Fr_std with std: raw 256-bit integers used verbatim) -> normalised projective rows, or affine"""
+    scalars = _fr(scalars)
+    require_gpu()
+    out = _scl_out(curve, scalars.shape[0], affine)
+    _scl_rc(load().zkg_g1_scl_fixed(CURVE_ID[curve], scalars.shape[0], _p(scalars), 0 if std else 1,
+                                    _p(_g1_aff(curve, base, "scalar_mul_fixed")), 1 if affine else 0, _p(out)),
+            "scalar_mul_fixed")
+    return out
+
+
+def scalar_mul_fixed_device(curve, n, d_scalars, base, d_tgt, std=False, affine=False):
+    """device-resident scalar_mul_fixed (zkg_g1_scl_fixed_device): the base stays a host row"""
+    return load().zkg_g1_scl_fixed_device(CURVE_ID[curve], n, d_scalars.ptr, 0 if std else 1,
+                                          _p(_g1_aff(curve, base, "scalar_mul_fixed")), 1 if affine else 0, d_tgt.ptr)
+
+
+def scalar_mul_rows(curve, scalars, bases, std=False, affine=False):
+    """[k_i] P_i: zipWith scalarMul over n affine rows (all-0xFF rows stay infinity)"""
+    scalars = _fr(scalars)
+    bases = np.ascontiguousarray(bases, dtype=np.uint64)
+    if bases.ndim != 2 or bases.shape != (scalars.shape[0], 2 * NLIMBS_P[curve]):
+        raise ValueError("scalar_mul_rows: incompatible array dimensions")
+    require_gpu()
+    out = _scl_out(curve, scalars.shape[0], affine)
+    _scl_rc(load().zkg_g1_scl_rows(CURVE_ID[curve], scalars.shape[0], _p(scalars), 0 if std else 1, _p(bases),
+                                   1 if affine else 0, _p(out)), "scalar_mul_rows")
+    return out
+
+
+def scalar_mul_rows_device(curve, n, d_scalars, d_bases, d_tgt, std=False, affine=False):
+    """device-resident scalar_mul_rows (zkg_g1_scl_rows_device)"""
+    return load().zkg_g1_scl_rows_device(CURVE_ID[curve], n, d_scalars.ptr, 0 if std else 1, d_bases.ptr,
+                                         1 if affine else 0, d_tgt.ptr)
+
+
+def srs_powers(curve, tau, n, base, a=None, affine=False):
+    """[a tau^i] P, i < n: the `taus` of mkKZGSetup (examples/KZG.hs:59-62); tau, a Montgomery Fr (a None = 1)"""
+    require_gpu()
+    out = _scl_out(curve, n, affine)
+    _scl_rc(load().zkg_g1_scl_powers(CURVE_ID[curve], n, _p(_k(a)) if a is not None else None, _p(_k(tau)),
+                                     _p(_g1_aff(curve, base, "srs_powers")), 1 if affine else 0, _p(out)),
+            "srs_powers")
+    return out
+
+
+def srs_powers_device(curve, n, tau, base, d_tgt, a=None, affine=False):
+    """device-resident srs_powers (zkg_g1_scl_powers_device): the scalars are made on the device"""
+    return load().zkg_g1_scl_powers_device(CURVE_ID[curve], n, _p(_k(a)) if a is not None else None, _p(_k(tau)),
+                                           _p(_g1_aff(curve, base, "srs_powers")), 1 if affine else 0, d_tgt.ptr)
+
+
+def scl_set_window(c):
+    """test hook: window of the fixed-base table (0 restores the default; clamped to 2..16)"""
+    load().zkg_g1_scl_set_window(int(c))
+
+
+def scl_set_fixed_min(n):
+    """test hook: fixed-base calls below n rows take the per-row kernel (< 0 default, 0 never)"""
+    load().zkg_g1_scl_set_fixed_min(int(n))
+
+
+def scl_last_path():
+    """0: the most recent fixed-base call ran the per-row kernel; otherwise the window of its table path"""
+    return load().zkg_g1_scl_last_path()
+
+
+def scl_digits(c, k):
+    """the fixed-base kernel's signed c-bit recoding of the 256-bit integer k (4 words): a list of
+    ceil(257 / c) digits with sum d_w 2^(c w) = k; no GPU call"""
+    buf = (ctypes.c_int * 129)()
+    w = load().zkg_g1_scl_digits(int(c), _p(_k(k)), buf, 129)
+    if w < 0:
+        raise ValueError("scl_digits: the window must be in 2..16")
+    return list(buf[:w])
+
+
+def scl_table_bytes(curve, c):
+    """bytes of the fixed-base table for window c; no GPU call"""
+    return load().zkg_g1_scl_table_bytes(CURVE_ID[curve], int(c))
+
+
+@dataclass
+class KZGSetup:
+    """Mirror of examples/KZG.hs KZGSetup: the point arrays stay on the device (projective rows)"""
+    domain: FFTSubgroup
+    tau_g1s: "DeviceBuffer"
+    lagrange_taus: "DeviceBuffer"
+    g2_tau_g2: tuple
+
+    def free(self):
+        self.tau_g1s.free()
+        self.lagrange_taus.free()
+
+
+def kzg_setup(curve, tau, log_size, g1, g2):
+    """mkKZGSetup (examples/KZG.hs:42-62): tauG1s = [tau^i] g1 (srs_powers), lagrangeTaus = curveIFFT of it
+    (the device group FFT reads the first buffer where it lies) and (g2, tau g2) by the G2 MSM of one pair;
+    g1 affine G1, g2 affine G2, tau Montgomery Fr"""
+    require_gpu()
+    dom = get_fft_subgroup(curve, log_size)
+    n = dom.size
+    nbytes = n * 3 * NLIMBS_P[curve] * 8
+    taus, lag = DeviceBuffer.empty(nbytes), DeviceBuffer.empty(nbytes)
+    try:
+        _scl_rc(srs_powers_device(curve, n, tau, g1, taus), "kzg_setup")
+        g1_fft_device(curve, log_size, dom.gen_array(), taus, lag, inverse=True)
+        g2 = np.ascontiguousarray(g2, dtype=np.uint64).reshape(1, -1)
+        tau_g2 = g2_msm(curve, _k(tau).reshape(1, 4), g2)
+    except Exception:
+        taus.free()
+        lag.free()
+        raise
+    return KZGSetup(dom, taus, lag, (g2.reshape(-1), tau_g2))
 
 
 def poly_mul_device(curve, n1, d_a, n2, d_b, d_tgt):
