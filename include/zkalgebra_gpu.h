@@ -490,6 +490,36 @@ ZKG_API int  zkg_g1_scl_digits(int c, const uint64_t k[4], int *digits, int cap)
  * words (no GPU call); 0 for an unknown curve */
 ZKG_API size_t zkg_g1_scl_table_bytes(int curve, int c);
 
+/* Batch G2 scalar multiplication: the mirror of the G1 set above on the twist (the reference's
+ * <C>_G2_proj_scl_Fr_mont / _scl_Fr_std, G2_proj.c:453-480, followed by _normalize or _to_affine, once per
+ * row).  Same arguments, same return codes, same scalar rows.  A coordinate is an Fp2 element c0 || c1, so
+ * here NP = 8 (BN128) / 12 (BLS12-381) words: an affine row x.c0 x.c1 y.c0 y.c1 is 2 NP words (all-0xFF =
+ * infinity), a target row 3 NP (affine_out = 0: (x : y : 1), infinity (0 : 1 : 0)) or 2 NP words
+ * (affine_out = 1).  Contract: the multiplication is by the INTEGER value of the scalar -- nothing is reduced
+ * mod r -- so the rows equal the reference's for every on-curve base, also outside the order-r subgroup of
+ * the twist (both twists have a cofactor).  No reference special case arises on G2: neither twist order
+ * has a factor <= 7, so every row is the group's multiple (DESIGN.md "Batch G2 scalar multiplication").
+ * Returns 0, or -1 with nothing written for n < 0 or an unknown curve; n == 0 is a no-op. */
+ZKG_API int zkg_g2_scl_fixed_device(int curve, int n, const uint64_t *d_expos, int expos_mont,
+                                    const uint64_t *base_affine, int affine_out, uint64_t *d_tgt);  /* DEVICE expos, tgt */
+ZKG_API int zkg_g2_scl_fixed(int curve, int n, const uint64_t *expos, int expos_mont, const uint64_t *base_affine,
+                             int affine_out, uint64_t *tgt);                                        /* HOST pointers */
+ZKG_API int zkg_g2_scl_rows_device(int curve, int n, const uint64_t *d_expos, int expos_mont, const uint64_t *d_bases,
+                                   int affine_out, uint64_t *d_tgt);                                /* DEVICE pointers */
+ZKG_API int zkg_g2_scl_rows(int curve, int n, const uint64_t *expos, int expos_mont, const uint64_t *bases,
+                            int affine_out, uint64_t *tgt);                                         /* HOST pointers */
+ZKG_API int zkg_g2_scl_powers_device(int curve, int n, const uint64_t *a, const uint64_t *tau,
+                                     const uint64_t *base_affine, int affine_out, uint64_t *d_tgt); /* DEVICE tgt */
+ZKG_API int zkg_g2_scl_powers(int curve, int n, const uint64_t *a, const uint64_t *tau, const uint64_t *base_affine,
+                              int affine_out, uint64_t *tgt);                                       /* HOST tgt */
+/* test hooks of the G2 entries, as the G1 ones, with a state of their own (the defaults differ per group) */
+ZKG_API void zkg_g2_scl_set_window(int c);
+ZKG_API void zkg_g2_scl_set_fixed_min(int n);
+ZKG_API int  zkg_g2_scl_last_path(void);
+/* bytes of the G2 fixed-base table for window c (clamped to 2..16): 2^(c-1) ceil(257 / c) rows of 2 NP
+ * words (no GPU call); 0 for an unknown curve */
+ZKG_API size_t zkg_g2_scl_table_bytes(int curve, int c);
+
 /* host helpers on G1 (projective, reference Montgomery form) */
 ZKG_API void zkg_g1_proj_add(int curve, const uint64_t *a, const uint64_t *b, uint64_t *out);
 ZKG_API void zkg_g1_proj_normalize(int curve, const uint64_t *a, uint64_t *out);

@@ -312,7 +312,7 @@ ZKG_API void zkg_g1_jac_batch_to_affine_device(int curve, int n, const uint64_t 
 
 }  // extern "C"
 
-// ---------------------------------------------------------------------------- G1 batch scalar multiplication
+// ---------------------------------------------------------------------------- G1 and G2 batch scalar multiplication
 // a host loop over <C>_G1_proj_scl_Fr_mont / _scl_Fr_std (bls12_381_G1_proj.c:462-489) and normalize / to_affine
 #include "zk_scl.hpp"
 
@@ -361,6 +361,31 @@ ZKG_API int zkg_g1_scl_digits(int c, const uint64_t k[4], int *digits, int cap) 
 }
 ZKG_API size_t zkg_g1_scl_table_bytes(int curve, int c) {
   return curve == ZKG_BN128 || curve == ZKG_BLS12_381 ? zk::g1_scl_table_bytes(curve, c) : 0;
+}
+
+// the same on G2: <C>_G2_proj_scl_Fr_mont / _scl_Fr_std (bls12_381_G2_proj.c:453-480) and normalize / to_affine
+ZKG_SCL_ENTRY(zkg_g2_scl_fixed_device, g2_scl_fixed, false)
+ZKG_SCL_ENTRY(zkg_g2_scl_fixed, g2_scl_fixed, true)
+ZKG_SCL_ENTRY(zkg_g2_scl_rows_device, g2_scl_rows, false)
+ZKG_SCL_ENTRY(zkg_g2_scl_rows, g2_scl_rows, true)
+
+ZKG_API int zkg_g2_scl_powers_device(int curve, int n, const uint64_t *a, const uint64_t *tau,
+                                     const uint64_t *base_affine, int affine_out, uint64_t *d_tgt) {
+  if (!scl_args_ok(curve, n)) return -1;
+  guard([&] { zk::g2_scl_powers(curve, n, a, tau, base_affine, affine_out != 0, d_tgt, false); });
+  return 0;
+}
+ZKG_API int zkg_g2_scl_powers(int curve, int n, const uint64_t *a, const uint64_t *tau, const uint64_t *base_affine,
+                              int affine_out, uint64_t *tgt) {
+  if (!scl_args_ok(curve, n)) return -1;
+  guard([&] { zk::g2_scl_powers(curve, n, a, tau, base_affine, affine_out != 0, tgt, true); });
+  return 0;
+}
+ZKG_API void zkg_g2_scl_set_window(int c) { zk::g2_scl_set_window(c); }
+ZKG_API void zkg_g2_scl_set_fixed_min(int n) { zk::g2_scl_set_fixed_min(n); }
+ZKG_API int zkg_g2_scl_last_path(void) { return zk::g2_scl_last_path(); }
+ZKG_API size_t zkg_g2_scl_table_bytes(int curve, int c) {
+  return curve == ZKG_BN128 || curve == ZKG_BLS12_381 ? zk::g2_scl_table_bytes(curve, c) : 0;
 }
 
 }  // extern "C"

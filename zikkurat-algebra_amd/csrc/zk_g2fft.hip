@@ -198,8 +198,9 @@ __global__ void __launch_bounds__(256) k_g2_fft_norm_chain(int n, int CHK, const
 }
 
 // one thread per point: 1 / ZZZ = conj(ZZZ) / N(ZZZ), 1 / Z = ZZ / ZZZ, x = X / Z^2, y = Y / ZZZ, written
-// as the normalised reference row at bitrev_m(i) when bitrev_m > 0 (the inverse's output order)
-template <class C>
+// as the normalised reference row at bitrev_m(i) when bitrev_m > 0 (the inverse's output order); AFF: the
+// affine row x || y instead, all-0xFF at infinity (<C>_G2_proj_to_affine, G2_proj.c:139-151)
+template <class C, bool AFF>
 __global__ void __launch_bounds__(256) k_g2_fft_norm_apply(int n, int bitrev_m, const uint32_t *__restrict__ A,
                                                            const uint64_t *__restrict__ ninv,
                                                            uint64_t *__restrict__ tgt) {
@@ -233,6 +234,17 @@ __global__ void __launch_bounds__(256) k_g2_fft_norm_apply(int n, int bitrev_m, 
 #pragma unroll
   for (int l = 0; l < B::NW; l++) zeros[l] = 0;
   const size_t o = bitrev_m > 0 ? (size_t)(__builtin_bitreverse32((uint32_t)i) >> (32 - bitrev_m)) : i;
+  if constexpr (AFF) {
+    uint32_t ones[B::NW];
+#pragma unroll
+    for (int l = 0; l < B::NW; l++) ones[l] = ~0u;
+    uint64_t *q = tgt + o * 2 * NP;
+    st_ref_or(q, x0, fin, ones);
+    st_ref_or(q + NB, x1, fin, ones);
+    st_ref_or(q + NP, y0, fin, ones);
+    st_ref_or(q + NP + NB, y1, fin, ones);
+    return;
+  }
   uint64_t *q = tgt + o * 3 * NP;
   st_ref_or(q, x0, fin, zeros);  // infinity: (0 : 1 : 0), G2_proj.c:72-76
   st_ref_or(q + NB, x1, fin, zeros);
@@ -252,6 +264,19 @@ constexpr int G2_FFT_MAX_LOG = 24;
 // lanes); a lane's table is 10 KB on BLS12-381, 7.5 KB on BN254
 constexpr size_t G2_FFT_LANES = (size_t)1 << 16;
 static std::atomic<size_t> g2_fft_max_lanes{G2_FFT_LANES};
+
+// chain and apply over the n XYZZ rows A -> tgt (ninv: n NP / 2 words of scratch)
+template <class C, bool AFF>
+static void g2_norm_launch(hipStream_t st, size_t N, int bitrev_m, const uint32_t *A, uint64_t *ninv, uint64_t *tgt) {
+  const int chk = norm_chk(N);  // rows per shared inversion, as the batch conversions
+  const size_t nlanes = (N + chk - 1) / chk;
+  hipLaunchKernelGGL(k_g2_fft_norm_chain<C>, dim3(div_up(nlanes, 256)), dim3(256), 0, st, (int)N, chk, A, ninv,
+                     (int)nlanes);
+  ZK_CHECK(hipGetLastError());
+  hipLaunchKernelGGL((k_g2_fft_norm_apply<C, AFF>), dim3(div_up(N, 256)), dim3(256), 0, st, (int)N, bitrev_m, A, ninv,
+                     tgt);
+  ZK_CHECK(hipGetLastError());
+}
 
 template <class C>
 static void g2_fft_t(Device &dev, int m, const uint64_t *gen, const uint64_t *src, uint64_t *tgt, bool host_io,
@@ -297,19 +322,21 @@ static void g2_fft_t(Device &dev, int m, const uint64_t *gen, const uint64_t *sr
       std::swap(A, Bf);
     }
   }
-  const int chk = norm_chk(N);  // rows per shared inversion, as the batch conversions
-  const size_t nlanes = (N + chk - 1) / chk;
-  hipLaunchKernelGGL(k_g2_fft_norm_chain<C>, dim3(div_up(nlanes, 256)), dim3(256), 0, st, (int)N, chk, A, ninv,
-                     (int)nlanes);
-  ZK_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_g2_fft_norm_apply<C>, dim3(div_up(N, 256)), dim3(256), 0, st, (int)N, inverse ? m : 0, A, ninv,
-                     io.out);
-  ZK_CHECK(hipGetLastError());
+  g2_norm_launch<C, false>(st, N, inverse ? m : 0, A, ninv, io.out);
   io.finish();
 }
 
 // ---------------------------------------------------------------------------- public
 
+void g2_norm_xyzz_enqueue(int curve, hipStream_t st, int n, const uint32_t *src, uint64_t *scratch, uint64_t *tgt,
+                          bool affine) {
+  if (n <= 0) return;
+  on_curve<BN254_G2, BLS381_G2>(curve, [&](auto c) {
+    using C = decltype(c);
+    if (affine) g2_norm_launch<C, true>(st, (size_t)n, 0, src, scratch, tgt);
+    else g2_norm_launch<C, false>(st, (size_t)n, 0, src, scratch, tgt);
+  });
+}
 void g2_fft(int curve, int m, const uint64_t *gen, const uint64_t *src, uint64_t *tgt, bool host_io, bool inverse) {
   ZK_REQUIRE(m >= 0 && m <= G2_FFT_MAX_LOG, "G2 fft: log2 size out of range (0..24)");
   with_g2(curve, [&](Device &dev, auto c) { g2_fft_t<decltype(c)>(dev, m, gen, src, tgt, host_io, inverse); });

@@ -67,4 +67,12 @@ __device__ __forceinline__ void g2_inv_from_norm(Fe<F> &zi, const Fe<typename F:
   f2_join(zi, c0, c1);
 }
 
+// the G2 group FFT's closing normalisation on its own, enqueued on st (zk_g2fft.hip, k_g2_fft_norm_chain /
+// k_g2_fft_norm_apply): n G2 XYZZ rows `src` (ZZZ = 0: infinity) -> rows (x : y : 1) / (0 : 1 : 0) of 3 NP
+// words as <C>_G2_proj_normalize writes them, or with `affine` rows x || y of 2 NP words, all-0xFF at
+// infinity, as _to_affine does (NP: the words of an Fp2 element); scratch: n NP / 2 words.  The twin of
+// g1_norm_xyzz_enqueue (zk_fftdev.hpp); the G2 scalar multiplications (zk_scl_g2_*.hip) end with it.
+void g2_norm_xyzz_enqueue(int curve, hipStream_t st, int n, const uint32_t *src, uint64_t *scratch, uint64_t *tgt,
+                          bool affine);
+
 }  // namespace zk

@@ -1,5 +1,6 @@
-// zk_scl.hpp -- C++ interface of the batch G1 scalar multiplications (zk_scl.hip), and the signed-window
-// recoding that the fixed-base kernel and the host hook zkg_g1_scl_digits share
+// zk_scl.hpp -- C++ interface of the batch scalar multiplications on G1 (zk_scl.hip) and G2
+// (zk_scl_g2_bn.hip, zk_scl_g2_bls.hip), and the signed-window recoding that the fixed-base kernel and the
+// host hook zkg_g1_scl_digits share
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -54,5 +55,20 @@ void g1_scl_powers(int curve, int n, const uint64_t *a, const uint64_t *tau, con
 void g1_scl_set_window(int c);
 void g1_scl_set_fixed_min(int n);
 int g1_scl_last_path();
+
+// The same on G2 (zk_scl_g2_bn.hip, zk_scl_g2_bls.hip): a coordinate is an Fp2 element c0 || c1, so NP is
+// twice the base field's word count -- an affine row 2 NP = 16 (BN254) / 24 (BLS12-381) words.  Same
+// contract: the integer value of the scalar, no reduction mod r, bases outside the order-r subgroup of the
+// twist allowed.  The hooks have a state of their own (the defaults differ per group).
+size_t g2_scl_table_bytes(int curve, int c);
+void g2_scl_fixed(int curve, int n, const uint64_t *expos, bool expos_mont, const uint64_t *base, bool affine_out,
+                  uint64_t *tgt, bool host_io);
+void g2_scl_rows(int curve, int n, const uint64_t *expos, bool expos_mont, const uint64_t *bases, bool affine_out,
+                 uint64_t *tgt, bool host_io);
+void g2_scl_powers(int curve, int n, const uint64_t *a, const uint64_t *tau, const uint64_t *base, bool affine_out,
+                   uint64_t *tgt, bool host_io);
+void g2_scl_set_window(int c);
+void g2_scl_set_fixed_min(int n);
+int g2_scl_last_path();
 
 }  // namespace zk

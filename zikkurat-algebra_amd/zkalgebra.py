@@ -89,6 +89,9 @@ EXTENSION_SYMBOLS += ["zkg_ntt_set_cache_limit", "zkg_ntt_cache_bytes"]
 EXTENSION_SYMBOLS += [f"zkg_g1_scl_{k}{d}" for k in ("fixed", "rows", "powers") for d in ("", "_device")] + [
     "zkg_g1_scl_set_window", "zkg_g1_scl_set_fixed_min", "zkg_g1_scl_last_path", "zkg_g1_scl_digits",
     "zkg_g1_scl_table_bytes"]
+# the same on G2
+EXTENSION_SYMBOLS += [f"zkg_g2_scl_{k}{d}" for k in ("fixed", "rows", "powers") for d in ("", "_device")] + [
+    "zkg_g2_scl_set_window", "zkg_g2_scl_set_fixed_min", "zkg_g2_scl_last_path", "zkg_g2_scl_table_bytes"]
 
 _lib = None
 
@@ -188,6 +191,17 @@ def load():
             lib.zkg_g1_scl_digits.argtypes = [ctypes.c_int, U64P, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
             lib.zkg_g1_scl_table_bytes.restype = ctypes.c_size_t
             lib.zkg_g1_scl_table_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+        if hasattr(lib, "zkg_g2_scl_fixed"):  # absent from an older variant build, as above
+            lib.zkg_g2_scl_fixed_device.argtypes = lib.zkg_g1_scl_fixed_device.argtypes
+            lib.zkg_g2_scl_rows_device.argtypes = lib.zkg_g1_scl_rows_device.argtypes
+            for f in (lib.zkg_g2_scl_fixed, lib.zkg_g2_scl_rows):
+                f.argtypes = lib.zkg_g1_scl_fixed.argtypes
+            lib.zkg_g2_scl_powers_device.argtypes = lib.zkg_g1_scl_powers_device.argtypes
+            lib.zkg_g2_scl_powers.argtypes = lib.zkg_g1_scl_powers.argtypes
+            lib.zkg_g2_scl_set_window.argtypes = [ctypes.c_int]
+            lib.zkg_g2_scl_set_fixed_min.argtypes = [ctypes.c_int]
+            lib.zkg_g2_scl_table_bytes.restype = ctypes.c_size_t
+            lib.zkg_g2_scl_table_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
         lib.zkg_last_error.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         lib.zkg_comm_unique_id.argtypes = [ctypes.c_void_p]
         lib.zkg_comm_init.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
@@ -1106,38 +1120,135 @@ def scl_table_bytes(curve, c):
     return load().zkg_g1_scl_table_bytes(CURVE_ID[curve], int(c))
 
 
+def _g2_aff(curve, base, name):
+    base = np.ascontiguousarray(base, dtype=np.uint64).reshape(-1)
+    if base.shape[0] != 4 * NLIMBS_P[curve]:
+        raise ValueError(f"{name}: the base must be one affine G2 point (x.c0, x.c1, y.c0, y.c1) in Montgomery form")
+    return base
+
+
+def _g2_scl_out(curve, n, affine):
+    return np.zeros((n, (4 if affine else 6) * NLIMBS_P[curve]), dtype=np.uint64)
+
+
+def g2_scalar_mul_fixed(curve, scalars, base, std=False, affine=False):
+    """scalar_mul_fixed on G2: [k_i] P for one affine G2 base (4 NLIMBS_P words; G2_proj_scl_Fr_mont, or
+    _scl_Fr_std with std) -> normalised projective rows (6 NLIMBS_P words), or affine (4 NLIMBS_P).  The
+    integer value of the scalar, no reduction mod r; bases outside the subgroup allowed."""
+    scalars = _fr(scalars)
+    base = _g2_aff(curve, base, "g2_scalar_mul_fixed")
+    require_gpu()
+    out = _g2_scl_out(curve, scalars.shape[0], affine)
+    _scl_rc(load().zkg_g2_scl_fixed(CURVE_ID[curve], scalars.shape[0], _p(scalars), 0 if std else 1, _p(base),
+                                    1 if affine else 0, _p(out)), "g2_scalar_mul_fixed")
+    return out
+
+
+def g2_scalar_mul_fixed_device(curve, n, d_scalars, base, d_tgt, std=False, affine=False):
+    """device-resident g2_scalar_mul_fixed (zkg_g2_scl_fixed_device): the base stays a host row"""
+    return load().zkg_g2_scl_fixed_device(CURVE_ID[curve], n, d_scalars.ptr, 0 if std else 1,
+                                          _p(_g2_aff(curve, base, "g2_scalar_mul_fixed")), 1 if affine else 0,
+                                          d_tgt.ptr)
+
+
+def g2_scalar_mul_rows(curve, scalars, bases, std=False, affine=False):
+    """[k_i] P_i on G2: n affine rows (all-0xFF rows stay infinity)"""
+    scalars = _fr(scalars)
+    bases = np.ascontiguousarray(bases, dtype=np.uint64)
+    if bases.ndim != 2 or bases.shape != (scalars.shape[0], 4 * NLIMBS_P[curve]):
+        raise ValueError("g2_scalar_mul_rows: incompatible array dimensions")
+    require_gpu()
+    out = _g2_scl_out(curve, scalars.shape[0], affine)
+    _scl_rc(load().zkg_g2_scl_rows(CURVE_ID[curve], scalars.shape[0], _p(scalars), 0 if std else 1, _p(bases),
+                                   1 if affine else 0, _p(out)), "g2_scalar_mul_rows")
+    return out
+
+
+def g2_scalar_mul_rows_device(curve, n, d_scalars, d_bases, d_tgt, std=False, affine=False):
+    """device-resident g2_scalar_mul_rows (zkg_g2_scl_rows_device)"""
+    return load().zkg_g2_scl_rows_device(CURVE_ID[curve], n, d_scalars.ptr, 0 if std else 1, d_bases.ptr,
+                                         1 if affine else 0, d_tgt.ptr)
+
+
+def g2_srs_powers(curve, tau, n, base, a=None, affine=False):
+    """[a tau^i] P, i < n, on G2 (a multi-point opening key, a Groth16 G2 column); tau, a Montgomery Fr (a None = 1)"""
+    base = _g2_aff(curve, base, "g2_srs_powers")
+    require_gpu()
+    out = _g2_scl_out(curve, n, affine)
+    _scl_rc(load().zkg_g2_scl_powers(CURVE_ID[curve], n, _p(_k(a)) if a is not None else None, _p(_k(tau)), _p(base),
+                                     1 if affine else 0, _p(out)), "g2_srs_powers")
+    return out
+
+
+def g2_srs_powers_device(curve, n, tau, base, d_tgt, a=None, affine=False):
+    """device-resident g2_srs_powers (zkg_g2_scl_powers_device): the scalars are made on the device"""
+    return load().zkg_g2_scl_powers_device(CURVE_ID[curve], n, _p(_k(a)) if a is not None else None, _p(_k(tau)),
+                                           _p(_g2_aff(curve, base, "g2_srs_powers")), 1 if affine else 0, d_tgt.ptr)
+
+
+def g2_scl_set_window(c):
+    """test hook: window of the G2 fixed-base table (0 restores the default; clamped to 2..16)"""
+    load().zkg_g2_scl_set_window(int(c))
+
+
+def g2_scl_set_fixed_min(n):
+    """test hook: G2 fixed-base calls below n rows take the per-row kernel (< 0 default, 0 never)"""
+    load().zkg_g2_scl_set_fixed_min(int(n))
+
+
+def g2_scl_last_path():
+    """0: the most recent G2 fixed-base call ran the per-row kernel; otherwise the window of its table path"""
+    return load().zkg_g2_scl_last_path()
+
+
+def g2_scl_table_bytes(curve, c):
+    """bytes of the G2 fixed-base table for window c; no GPU call"""
+    return load().zkg_g2_scl_table_bytes(CURVE_ID[curve], int(c))
+
+
 @dataclass
 class KZGSetup:
-    """Mirror of examples/KZG.hs KZGSetup: the point arrays stay on the device (projective rows)"""
+    """Mirror of examples/KZG.hs KZGSetup: the point arrays stay on the device (projective rows);
+    tau_g2s ([tau^i] g2, i < g2_powers) only when kzg_setup was asked for it"""
     domain: FFTSubgroup
     tau_g1s: "DeviceBuffer"
     lagrange_taus: "DeviceBuffer"
     g2_tau_g2: tuple
+    tau_g2s: "DeviceBuffer" = None
 
     def free(self):
         self.tau_g1s.free()
         self.lagrange_taus.free()
+        if self.tau_g2s is not None:
+            self.tau_g2s.free()
 
 
-def kzg_setup(curve, tau, log_size, g1, g2):
+def kzg_setup(curve, tau, log_size, g1, g2, g2_powers=0):
     """mkKZGSetup (examples/KZG.hs:42-62): tauG1s = [tau^i] g1 (srs_powers), lagrangeTaus = curveIFFT of it
     (the device group FFT reads the first buffer where it lies) and (g2, tau g2) by the G2 MSM of one pair;
-    g1 affine G1, g2 affine G2, tau Montgomery Fr"""
+    g1 affine G1, g2 affine G2, tau Montgomery Fr.  g2_powers = k > 0: also tau_g2s, the k projective rows
+    [tau^i] g2 on the device (g2_srs_powers)."""
     require_gpu()
     dom = get_fft_subgroup(curve, log_size)
     n = dom.size
     nbytes = n * 3 * NLIMBS_P[curve] * 8
-    taus, lag = DeviceBuffer.empty(nbytes), DeviceBuffer.empty(nbytes)
+    bufs = [DeviceBuffer.empty(nbytes), DeviceBuffer.empty(nbytes)]
+    taus, lag = bufs
     try:
         _scl_rc(srs_powers_device(curve, n, tau, g1, taus), "kzg_setup")
         g1_fft_device(curve, log_size, dom.gen_array(), taus, lag, inverse=True)
         g2 = np.ascontiguousarray(g2, dtype=np.uint64).reshape(1, -1)
         tau_g2 = g2_msm(curve, _k(tau).reshape(1, 4), g2)
+        tau_g2s = None
+        if g2_powers > 0:
+            tau_g2s = DeviceBuffer.empty(g2_powers * 6 * NLIMBS_P[curve] * 8)
+            bufs.append(tau_g2s)
+            _scl_rc(g2_srs_powers_device(curve, g2_powers, tau, g2, tau_g2s), "kzg_setup")
     except Exception:
-        taus.free()
-        lag.free()
+        for b in bufs:
+            b.free()
         raise
-    return KZGSetup(dom, taus, lag, (g2.reshape(-1), tau_g2))
+    return KZGSetup(dom, taus, lag, (g2.reshape(-1), tau_g2), tau_g2s)
 
 
 def poly_mul_device(curve, n1, d_a, n2, d_b, d_tgt):
