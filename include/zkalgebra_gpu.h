@@ -586,6 +586,30 @@ ZKG_API int zkg_g1_fft_radix_products(int b);
 ZKG_API size_t zkg_msm_workspace_bytes(int curve, int npoints, int expo_nlimbs, int expos_mont, int host_inputs,
                                        int window_size, int groups);
 
+/* Batch optimal-ate pairings (the reference's <C>_pairing_affine / _pairing_projective / _pairing_final_expo,
+ * lib/cbits/curves/pairing/<C>_pairing.c), NP = 4 (BN128) or 6 (BLS12-381) u64 words per Fp:
+ *   P rows    affine G1, 2 NP words (x || y, Montgomery form); all-0xFF = infinity
+ *   Q rows    affine G2, 4 NP words (x.c0 x.c1 y.c0 y.c1); all-0xFF = infinity
+ *   Fp12 rows 12 NP words, 2 x 3 x 2 Fp in Montgomery form (the reference's Fp12 layout)
+ * Every row equals <C>_pairing_affine(P_i, Q_i) bit for bit; a row whose P or Q is infinity gives Montgomery
+ * one.  Domain: the rows are on-curve points of the order-r subgroups, or infinity.  For any other input the
+ * result is unspecified, but the call terminates and does not fault (every trip count is fixed); there is no
+ * subgroup or on-curve check.
+ * zkg_pairing_product: one Fp12 row, prod_i pairing(P_i, Q_i), with a single final exponentiation over the
+ * device-side product of the Miller values (infinity rows contribute one; n = 0 gives one).
+ * zkg_pairing_final_expo: row i = src_i^((p^12 - 1)/r) = <C>_pairing_final_expo for nonzero rows.
+ * Return 0, or -1 (negative n, unknown curve, null buffer, device error; the error channel has the text). */
+ZKG_API void bn128_pairing_affine(const uint64_t *P, const uint64_t *Q, uint64_t *tgt);
+ZKG_API void bn128_pairing_projective(const uint64_t *P, const uint64_t *Q, uint64_t *tgt);
+ZKG_API void bls12_381_pairing_affine(const uint64_t *P, const uint64_t *Q, uint64_t *tgt);
+ZKG_API void bls12_381_pairing_projective(const uint64_t *P, const uint64_t *Q, uint64_t *tgt);
+ZKG_API int zkg_pairing_rows(int curve, int n, const uint64_t *P, const uint64_t *Q, uint64_t *tgt);
+ZKG_API int zkg_pairing_rows_device(int curve, int n, const uint64_t *d_P, const uint64_t *d_Q, uint64_t *d_tgt);
+ZKG_API int zkg_pairing_product(int curve, int n, const uint64_t *P, const uint64_t *Q, uint64_t *tgt);
+ZKG_API int zkg_pairing_product_device(int curve, int n, const uint64_t *d_P, const uint64_t *d_Q, uint64_t *d_tgt);
+ZKG_API int zkg_pairing_final_expo(int curve, int n, const uint64_t *src, uint64_t *tgt);
+ZKG_API int zkg_pairing_final_expo_device(int curve, int n, const uint64_t *d_src, uint64_t *d_tgt);
+
 /* timing probe of the dominant kernel (MSM bucket accumulation / NTT pass chain),
  * measured with HIP events on each device's own stream; read sums over devices */
 ZKG_API void zkg_timer_enable(int on);

@@ -123,6 +123,44 @@ def unsat_block(name, p):
     return out
 
 
+def pairing_block(c, p, b):
+    """Constants of the pairing tower (zk_tower.hpp), computed from p: Fp2 = Fp[u]/(u^2 + 1),
+    Fp12 = Fp2[w]/(w^6 - xi); gamma_k = xi^(k (p - 1)/6), k < 6 (Frobenius of w^k), the twist coefficient
+    b' = b / xi (BN254, D-type) or b xi (BLS12-381, M-type), and one: eight Fp2 values in the internal radix."""
+    RB, NU = UNSAT[f"{c}_fp"]
+    Ri = 1 << (RB * NU)
+    xi = (9, 1) if c == "bn128" else (1, 1)
+    mul = lambda a, b: ((a[0] * b[0] - a[1] * b[1]) % p, (a[0] * b[1] + a[1] * b[0]) % p)
+    def power(a, e):
+        r = (1, 0)
+        while e:
+            if e & 1:
+                r = mul(r, a)
+            a = mul(a, a)
+            e >>= 1
+        return r
+    assert (p - 1) % 6 == 0
+    assert power(xi, (p * p - 1) // 2) != (1, 0) and power(xi, (p * p - 1) // 3) != (1, 0), "w^6 - xi is irreducible"
+    g1 = power(xi, (p - 1) // 6)
+    consts = [(1, 0)]
+    for _ in range(5):
+        consts.append(mul(consts[-1], g1))
+    n = pow(xi[0] * xi[0] + xi[1] * xi[1], -1, p)
+    xi_inv = (xi[0] * n % p, -xi[1] * n % p)
+    consts.append(mul((b, 0), xi_inv if c == "bn128" else xi))
+    consts.append((1, 0))
+    words = []
+    for a in consts:
+        for v in a:
+            words += limbs(v * Ri % p, NU, RB)
+    vals = ", ".join("0x%08xu" % w for w in words)
+    C = c.upper()
+    return [f"// pairing tower: gamma_0 .. gamma_5, b', one (Fp2 each, internal radix, c0 || c1)",
+            f"#define ZK_{C}_PAIR_CONSTS {{ {vals} }}",
+            f"#define ZK_{C}_PAIR_XI_A {xi[0]}",
+            f"#define ZK_{C}_PAIR_DTYPE {1 if c == 'bn128' else 0}"]
+
+
 def main():
     lines = ["// GENERATED by tools/gen_params.py -- do not edit by hand.",
              "// Constants derived from the public curve definitions; cross-checked",
@@ -153,6 +191,7 @@ def main():
         arr("FFT_GEN_FR64", mont(g, Rr, r), n64r)
         lines.append(f"#define ZK_{C}_FFT_LOG {L}")
         arr("HALF_FR64", mont(pow(2, -1, r), Rr, r), n64r)
+        lines += pairing_block(c, p, d["B"])
         lines.append("")
     here = os.path.dirname(os.path.abspath(__file__))
     dst = os.path.join(here, "..", "zikkurat-algebra_amd", "csrc", "zk_params.inc")

@@ -20,6 +20,12 @@ independent restatement in oracle/zk_oracle.c is checked equal by the tests).
   python tools/make_golden.py patterns  # adversarial NTT inputs (tests/golden_io.py NTT_PATTERNS) at
                                         # m = 5, 12, 14, 20 and random 2^20 vectors: reference forward /
                                         # inverse SHA-256 digests -> tests/golden/ntt_patterns.json   ~1 min
+  python tools/make_golden.py pairing /path/to/libzkpairing.so
+                                        # pairing rows and final exponentiations, both curves
+                                        # -> tests/golden/pairing_<curve>.npz.  The library is the reference's
+                                        # lib/cbits with its Fp6 / Fp12 / pairing sources added to the list of
+                                        # oracle/Makefile, built outside the repository the same way (clang
+                                        # -O2, no -DARCH_*).                                          ~1 s
 
 Only this script (in this container, where /root/reference exists) runs the reference;
 the GPU box only reads the committed .npz/.json files.
@@ -366,6 +372,90 @@ def make_g2_large():
         print(k, "reference %.1fs" % v["reference_seconds"], flush=True)
 
 
+# ----------------------------------------------------------------------------- pairing
+
+PAIRING_SEED = 0x5A4B00F8
+# families of equal a b mod r: (2,3) (3,2) (6,1) (1,6); (4,5) (10,2) (20,1); one of 256-bit random factors
+PAIRING_SMALL = [[(2, 3), (3, 2), (6, 1), (1, 6)], [(4, 5), (10, 2), (20, 1)]]
+
+
+def make_pairing(libpath):
+    """<C>_pairing_affine on ([a] g1, [b] g2) rows and <C>_pairing_final_expo on random Fp12 rows.  Points
+    come from the _ref library's <C>_G1_affine_scl_Fr_std / <C>_G2_affine_scl_Fr_std on the generators."""
+    import ctypes
+    import random
+    os.makedirs(GOLD, exist_ok=True)
+    plib = ctypes.CDLL(libpath)
+    ref = Reference()
+    U64P = ctypes.POINTER(ctypes.c_uint64)
+    ptr = lambda a: a.ctypes.data_as(U64P)
+    ff = np.uint64(0xFFFFFFFFFFFFFFFF)
+    for curve in zk.CURVES:
+        NP = zk.NLIMBS_P[curve]
+        r = R_ORDER[curve]
+        rnd = random.Random(PAIRING_SEED + NP)
+        g1 = np.array((ctypes.c_uint64 * (2 * NP)).in_dll(ref.lib, f"{curve}_G1_affine_gen_G1"), dtype=np.uint64)
+        g2 = np.array((ctypes.c_uint64 * (4 * NP)).in_dll(ref.lib, f"{curve}_G2_affine_gen_G2"), dtype=np.uint64)
+        pfield = {4: 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47,
+                  6: 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB}[NP]
+
+        def mul(a, b):
+            P = np.zeros(2 * NP, dtype=np.uint64)
+            Q = np.zeros(4 * NP, dtype=np.uint64)
+            ref.arr(curve, "G1_affine_scl_Fr_std", limbs(a), g1, P)
+            ref.arr(curve, "G2_affine_scl_Fr_std", limbs(b), g2, Q)
+            return P, Q
+
+        fams = [list(f) for f in PAIRING_SMALL]
+        big = []
+        a, b = rnd.getrandbits(256), rnd.getrandbits(256)
+        c = rnd.getrandbits(256)
+        big.append((a % r, b % r))
+        big.append((a * b % r, 1))
+        big.append((c % r, a * b * pow(c, -1, r) % r))
+        fams.append(big)
+        fams.append([(1, 1)])                                         # the generators themselves
+        fams += [[(rnd.randrange(1, r), rnd.randrange(1, r))] for _ in range(4)]
+        Ps, Qs, family, factors = [], [], [], []
+        for fi, fam in enumerate(fams):
+            for a, b in fam:
+                P, Q = mul(a, b)
+                Ps.append(P); Qs.append(Q); family.append(fi); factors.append(limbs(a).tolist() + limbs(b).tolist())
+        # a row and its G1-negated twin: rows twin[0] and twin[1]
+        P, Q = mul(7, 11)
+        y = sum(int(P[NP + j]) << (64 * j) for j in range(NP))
+        Pn = P.copy(); Pn[NP:] = limbs((pfield - y) % pfield, NP)
+        twin = [len(Ps), len(Ps) + 1]
+        for pp in (P, Pn):
+            Ps.append(pp); Qs.append(Q); family.append(len(fams) + (0 if pp is P else 1)); factors.append([0] * 8)
+        # infinities: P, Q, both
+        P, Q = mul(5, 9)
+        infs = []
+        for pi, qi in ((True, False), (False, True), (True, True)):
+            infs.append(len(Ps))
+            Ps.append(np.full(2 * NP, ff) if pi else P); Qs.append(np.full(4 * NP, ff) if qi else Q)
+            family.append(-1); factors.append([0] * 8)
+        Ps, Qs = np.array(Ps, dtype=np.uint64), np.array(Qs, dtype=np.uint64)
+        assert Ps.shape[0] <= 48
+        out = np.zeros((Ps.shape[0], 12 * NP), dtype=np.uint64)
+        t = time.time()
+        for i in range(Ps.shape[0]):
+            getattr(plib, f"{curve}_pairing_affine")(ptr(Ps[i]), ptr(Qs[i]), ptr(out[i]))
+        dt = time.time() - t
+        # random nonzero Fp12 rows in Montgomery form (any canonical words are some element's)
+        src = np.array([[w for _ in range(12) for w in limbs(rnd.randrange(1, pfield), NP)] for _ in range(8)],
+                       dtype=np.uint64)
+        fe = np.zeros_like(src)
+        for i in range(8):
+            getattr(plib, f"{curve}_pairing_final_expo")(ptr(src[i]), ptr(fe[i]))
+        np.savez_compressed(os.path.join(GOLD, f"pairing_{curve}.npz"), P=Ps, Q=Qs, pairing=out,
+                            family=np.array(family, dtype=np.int64), factors=np.array(factors, dtype=np.uint64),
+                            twin=np.array(twin, dtype=np.int64), infinity=np.array(infs, dtype=np.int64),
+                            fe_src=src, fe_out=fe)
+        print(curve, Ps.shape[0], "pairing rows, 8 final exponentiations; reference %.2f ms per pairing" %
+              (1e3 * dt / Ps.shape[0]))
+
+
 def make_large(which):
     os.makedirs(GOLD, exist_ok=True)
     path = os.path.join(GOLD, "baseline_configs.json")
@@ -391,7 +481,7 @@ def make_large(which):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) < 2 or sys.argv[1] not in ("small", "large", "patterns", "groupfft", "g2large"):
+    if len(sys.argv) < 2 or sys.argv[1] not in ("small", "large", "patterns", "groupfft", "g2large", "pairing"):
         print(__doc__)
         sys.exit(2)
     if sys.argv[1] == "small":
@@ -402,5 +492,7 @@ if __name__ == "__main__":
         make_group_fft(sys.argv[2] if len(sys.argv) > 2 else None)
     elif sys.argv[1] == "g2large":
         make_g2_large()
+    elif sys.argv[1] == "pairing":
+        make_pairing(sys.argv[2])
     else:
         make_large(sys.argv[2] if len(sys.argv) > 2 else None)

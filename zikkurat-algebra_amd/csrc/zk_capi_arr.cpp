@@ -424,3 +424,46 @@ ZKG_API void zkg_g2_fft_device(int curve, int inverse, int m, const uint64_t *ge
 ZKG_API void zkg_g2_fft_set_max_lanes(int lanes) { zk::g2_fft_set_max_lanes(lanes); }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------- pairings
+// <C>_pairing_affine / _pairing_projective / _pairing_final_expo (bls12_381_pairing.c, bn128_pairing.c)
+#include "zk_pairing.hpp"
+
+extern "C" {
+
+#define ZKG_PAIRING_ENTRIES(PFX, CID)                                                                  \
+  ZKG_API void PFX##_pairing_affine(const uint64_t *P, const uint64_t *Q, uint64_t *tgt) {             \
+    guard([&] { zk::pairing_rows(CID, 1, P, Q, tgt, true); });                                         \
+  }                                                                                                    \
+  ZKG_API void PFX##_pairing_projective(const uint64_t *P, const uint64_t *Q, uint64_t *tgt) {         \
+    guard([&] { zk::pairing_projective(CID, P, Q, tgt); });                                            \
+  }
+ZKG_PAIRING_ENTRIES(bn128, ZKG_BN128)
+ZKG_PAIRING_ENTRIES(bls12_381, ZKG_BLS12_381)
+
+#define ZKG_PAIRING_ROWS(NAME, FN, HOST_IO)                                                            \
+  ZKG_API int NAME(int curve, int n, const uint64_t *P, const uint64_t *Q, uint64_t *tgt) {            \
+    return guard_ret<int>(-1, [&] {                                                                    \
+      zk::FN(curve, n, P, Q, tgt, HOST_IO);                                                            \
+      return 0;                                                                                        \
+    });                                                                                                \
+  }
+ZKG_PAIRING_ROWS(zkg_pairing_rows, pairing_rows, true)
+ZKG_PAIRING_ROWS(zkg_pairing_rows_device, pairing_rows, false)
+ZKG_PAIRING_ROWS(zkg_pairing_product, pairing_product, true)
+ZKG_PAIRING_ROWS(zkg_pairing_product_device, pairing_product, false)
+
+ZKG_API int zkg_pairing_final_expo(int curve, int n, const uint64_t *src, uint64_t *tgt) {
+  return guard_ret<int>(-1, [&] {
+    zk::pairing_final_expo(curve, n, src, tgt, true);
+    return 0;
+  });
+}
+ZKG_API int zkg_pairing_final_expo_device(int curve, int n, const uint64_t *d_src, uint64_t *d_tgt) {
+  return guard_ret<int>(-1, [&] {
+    zk::pairing_final_expo(curve, n, d_src, d_tgt, false);
+    return 0;
+  });
+}
+
+}  // extern "C"

@@ -92,6 +92,9 @@ EXTENSION_SYMBOLS += [f"zkg_g1_scl_{k}{d}" for k in ("fixed", "rows", "powers") 
 # the same on G2
 EXTENSION_SYMBOLS += [f"zkg_g2_scl_{k}{d}" for k in ("fixed", "rows", "powers") for d in ("", "_device")] + [
     "zkg_g2_scl_set_window", "zkg_g2_scl_set_fixed_min", "zkg_g2_scl_last_path", "zkg_g2_scl_table_bytes"]
+# pairings: the reference's single-pair symbols, and the batch / product / final-exponentiation extensions
+REFERENCE_SYMBOLS += [f"{c}_pairing_{k}" for c in CURVES for k in ("affine", "projective")]
+EXTENSION_SYMBOLS += [f"zkg_pairing_{k}{d}" for k in ("rows", "product", "final_expo") for d in ("", "_device")]
 
 _lib = None
 
@@ -191,6 +194,17 @@ def load():
             lib.zkg_g1_scl_digits.argtypes = [ctypes.c_int, U64P, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
             lib.zkg_g1_scl_table_bytes.restype = ctypes.c_size_t
             lib.zkg_g1_scl_table_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+        if hasattr(lib, "zkg_pairing_rows"):  # absent from an older variant build, as above
+            vp = ctypes.c_void_p  # host arrays and device addresses alike: never a truncated int
+            for k in ("rows", "product"):
+                for d in ("", "_device"):
+                    getattr(lib, f"zkg_pairing_{k}{d}").argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp]
+            for d in ("", "_device"):
+                getattr(lib, f"zkg_pairing_final_expo{d}").argtypes = [ctypes.c_int, ctypes.c_int, vp, vp]
+            for c in CURVES:
+                for k in ("affine", "projective"):
+                    getattr(lib, f"{c}_pairing_{k}").argtypes = [vp, vp, vp]
+                    getattr(lib, f"{c}_pairing_{k}").restype = None
         if hasattr(lib, "zkg_g2_scl_fixed"):  # absent from an older variant build, as above
             lib.zkg_g2_scl_fixed_device.argtypes = lib.zkg_g1_scl_fixed_device.argtypes
             lib.zkg_g2_scl_rows_device.argtypes = lib.zkg_g1_scl_rows_device.argtypes
@@ -1249,6 +1263,140 @@ def kzg_setup(curve, tau, log_size, g1, g2, g2_powers=0):
             b.free()
         raise
     return KZGSetup(dom, taus, lag, (g2.reshape(-1), tau_g2), tau_g2s)
+
+
+# ---------------------------------------------------------------------------- pairings
+# <C>_pairing_affine / _projective / _final_expo (lib/cbits/curves/pairing); Pairing.hs `pairing`
+
+FIELD_P = {
+    "bn128": 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47,
+    "bls12_381": 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB,
+}
+
+
+def _pair_rows(curve, P, Q, name, wp=2, wq=4):
+    """(P, Q, single): n rows of wp NP and wq NP words, or one row each"""
+    NP = NLIMBS_P[curve]
+    P = np.ascontiguousarray(P, dtype=np.uint64)
+    Q = np.ascontiguousarray(Q, dtype=np.uint64)
+    single = P.ndim == 1 and Q.ndim == 1
+    if single:
+        P, Q = P.reshape(1, -1), Q.reshape(1, -1)
+    if P.ndim != 2 or Q.ndim != 2 or P.shape[1] != wp * NP or Q.shape[1] != wq * NP or P.shape[0] != Q.shape[0]:
+        raise ValueError(f"{name}: incompatible array dimensions")
+    return P, Q, single
+
+
+def _pair_rc(rc, name):
+    if rc != 0:
+        raise ValueError(f"{name}: the call was refused ({last_error() or 'bad arguments'})")
+
+
+def fp12_one(curve):
+    """the Montgomery one of Fp12 as a row of 12 NP words; no GPU call"""
+    NP = NLIMBS_P[curve]
+    out = np.zeros(12 * NP, dtype=np.uint64)
+    v = (1 << (64 * NP)) % FIELD_P[curve]
+    out[:NP] = [(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(NP)]
+    return out
+
+
+def pairing(curve, P, Q):
+    """the optimal-ate pairing of affine G1 rows (2 NP words) and affine G2 rows (4 NP words): one pair, or n
+    pairs -> (n, 12 NP); row i equals <C>_pairing_affine(P_i, Q_i), an infinite P or Q gives one.  The rows are
+    points of the order-r subgroups (or infinity); nothing is checked."""
+    P, Q, single = _pair_rows(curve, P, Q, "pairing")
+    require_gpu()
+    out = np.zeros((P.shape[0], 12 * NLIMBS_P[curve]), dtype=np.uint64)
+    _pair_rc(load().zkg_pairing_rows(CURVE_ID[curve], P.shape[0], _p(P), _p(Q), _p(out)), "pairing")
+    return out[0] if single else out
+
+
+def pairing_device(curve, n, d_P, d_Q, d_tgt):
+    """device-resident pairing (zkg_pairing_rows_device)"""
+    return load().zkg_pairing_rows_device(CURVE_ID[curve], n, d_P.ptr if d_P else None, d_Q.ptr if d_Q else None,
+                                          d_tgt.ptr if d_tgt else None)
+
+
+def pairing_projective(curve, P, Q):
+    """<C>_pairing_projective: one projective G1 point (3 NP words) and one projective G2 point (6 NP words)"""
+    P, Q, _ = _pair_rows(curve, np.asarray(P).reshape(-1), np.asarray(Q).reshape(-1), "pairing_projective", 3, 6)
+    require_gpu()
+    out = np.zeros(12 * NLIMBS_P[curve], dtype=np.uint64)
+    getattr(load(), f"{curve}_pairing_projective")(_p(P), _p(Q), _p(out))
+    return out
+
+
+def pairing_product(curve, P, Q):
+    """prod_i pairing(P_i, Q_i) as one Fp12 row, with a single final exponentiation (no rows: one)"""
+    P, Q, _ = _pair_rows(curve, P, Q, "pairing_product")
+    require_gpu()
+    out = np.zeros(12 * NLIMBS_P[curve], dtype=np.uint64)
+    _pair_rc(load().zkg_pairing_product(CURVE_ID[curve], P.shape[0], _p(P), _p(Q), _p(out)), "pairing_product")
+    return out
+
+
+def pairing_product_device(curve, n, d_P, d_Q, d_tgt):
+    """device-resident pairing_product (zkg_pairing_product_device): d_tgt receives one Fp12 row"""
+    return load().zkg_pairing_product_device(CURVE_ID[curve], n, d_P.ptr if d_P else None, d_Q.ptr if d_Q else None,
+                                             d_tgt.ptr if d_tgt else None)
+
+
+def pairing_check(curve, P, Q):
+    """prod_i pairing(P_i, Q_i) == 1"""
+    return bool(np.array_equal(pairing_product(curve, P, Q), fp12_one(curve)))
+
+
+def final_expo(curve, src):
+    """x^((p^12 - 1)/r) per Fp12 row (<C>_pairing_final_expo); one row or (n, 12 NP)"""
+    src = np.ascontiguousarray(src, dtype=np.uint64)
+    single = src.ndim == 1
+    rows = src.reshape(1, -1) if single else src
+    if rows.ndim != 2 or rows.shape[1] != 12 * NLIMBS_P[curve]:
+        raise ValueError("final_expo: incompatible array dimensions")
+    require_gpu()
+    out = np.zeros_like(rows)
+    _pair_rc(load().zkg_pairing_final_expo(CURVE_ID[curve], rows.shape[0], _p(rows), _p(out)), "final_expo")
+    return out[0] if single else out
+
+
+def final_expo_device(curve, n, d_src, d_tgt):
+    """device-resident final_expo (zkg_pairing_final_expo_device)"""
+    return load().zkg_pairing_final_expo_device(CURVE_ID[curve], n, d_src.ptr if d_src else None,
+                                                d_tgt.ptr if d_tgt else None)
+
+
+def _g1_neg_proj(curve, pt):
+    """-(X : Y : Z): Y -> p - Y on the canonical Montgomery words"""
+    NP = NLIMBS_P[curve]
+    out = np.array(pt, dtype=np.uint64)
+    y = sum(int(out[NP + j]) << (64 * j) for j in range(NP))
+    y = (FIELD_P[curve] - y) % FIELD_P[curve]
+    out[NP:2 * NP] = [(y >> (64 * j)) & 0xFFFFFFFFFFFFFFFF for j in range(NP)]
+    return out
+
+
+def kzg_verify(curve, g1, g2, tau_g2, commitment, x0, y0, proof):
+    """verifyProof (examples/KZG.hs:120-124): pairing(proof, tau g2) == pairing(point, g2) with
+    point = commitment + [x0] proof - [y0] g1, evaluated as the two-row product
+    pairing(proof, tau g2) pairing(-point, g2) == 1.  g1 affine G1, g2 / tau_g2 affine G2, commitment and
+    proof projective G1 rows (what msm returns), x0 / y0 Montgomery Fr."""
+    NP = NLIMBS_P[curve]
+    g1 = _g1_aff(curve, g1, "kzg_verify")
+    g2 = np.ascontiguousarray(g2, dtype=np.uint64).reshape(-1)
+    tau_g2 = np.ascontiguousarray(tau_g2, dtype=np.uint64).reshape(-1)
+    commitment = np.ascontiguousarray(commitment, dtype=np.uint64).reshape(-1)
+    proof = np.ascontiguousarray(proof, dtype=np.uint64).reshape(-1)
+    if g2.shape[0] != 4 * NP or tau_g2.shape[0] != 4 * NP or commitment.shape[0] != 3 * NP or proof.shape[0] != 3 * NP:
+        raise ValueError("kzg_verify: incompatible array dimensions")
+    x0, y0 = _k(x0), _k(y0)
+    require_gpu()
+    proof_aff = g1_to_affine(curve, proof)
+    xq = scalar_mul_rows(curve, x0.reshape(1, 4), proof_aff.reshape(1, -1))[0]
+    yg = scalar_mul_fixed(curve, y0.reshape(1, 4), g1)[0]
+    point = g1_add(curve, g1_add(curve, commitment, xq), _g1_neg_proj(curve, yg))
+    neg_aff = g1_to_affine(curve, _g1_neg_proj(curve, point))
+    return pairing_check(curve, np.stack([proof_aff, neg_aff]), np.stack([tau_g2, g2]))
 
 
 def poly_mul_device(curve, n1, d_a, n2, d_b, d_tgt):
