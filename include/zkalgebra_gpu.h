@@ -594,7 +594,7 @@ ZKG_API size_t zkg_msm_workspace_bytes(int curve, int npoints, int expo_nlimbs, 
  * Every row equals <C>_pairing_affine(P_i, Q_i) bit for bit; a row whose P or Q is infinity gives Montgomery
  * one.  Domain: the rows are on-curve points of the order-r subgroups, or infinity.  For any other input the
  * result is unspecified, but the call terminates and does not fault (every trip count is fixed); there is no
- * subgroup or on-curve check.
+ * subgroup or on-curve check here (zkg_g1_check_rows / zkg_g2_check_rows below are that check).
  * zkg_pairing_product: one Fp12 row, prod_i pairing(P_i, Q_i), with a single final exponentiation over the
  * device-side product of the Miller values (infinity rows contribute one; n = 0 gives one).
  * zkg_pairing_final_expo: row i = src_i^((p^12 - 1)/r) = <C>_pairing_final_expo for nonzero rows.
@@ -609,6 +609,48 @@ ZKG_API int zkg_pairing_product(int curve, int n, const uint64_t *P, const uint6
 ZKG_API int zkg_pairing_product_device(int curve, int n, const uint64_t *d_P, const uint64_t *d_Q, uint64_t *d_tgt);
 ZKG_API int zkg_pairing_final_expo(int curve, int n, const uint64_t *src, uint64_t *tgt);
 ZKG_API int zkg_pairing_final_expo_device(int curve, int n, const uint64_t *d_src, uint64_t *d_tgt);
+
+/* Batch point validation: what a caller runs on points it was handed (a proof, a commitment, an SRS file)
+ * before the entries above, whose domain is the order-r subgroup.  Row i of `pts` is one point in the
+ * coordinate system `coords` (Montgomery words as everywhere; G1: NP = 4 / 6 words per coordinate, G2:
+ * NP = 8 / 12, c0 || c1), and flags[i] receives one byte:
+ *   ZKG_PT_CANONICAL    every coordinate, read as an integer (per Fp component), is < p; the affine all-0xFF
+ *                       row (infinity) is canonical too, and is the only row with a coordinate >= p that is.
+ *                       A row that is not canonical has the other three flags cleared, whatever its words.
+ *   ZKG_PT_ON_CURVE     the reference's <C>_G{1,2}_{affine,proj,jac}_is_on_curve of that coordinate system:
+ *   ZKG_PT_INFINITY     ... and its _is_infinity.  Affine infinity (all-0xFF) is on the curve; projective
+ *                       infinity is (0 : Y : 0) with Y != 0, so (X : Y : 0) with X != 0 and (0 : 0 : 0) are not on
+ *                       the curve; Jacobian infinity is (X : Y : 0) with Y^2 = X^3, X, Y != 0.
+ *   ZKG_PT_IN_SUBGROUP  ON_CURVE and [r]P = O; infinity is a member.  This is deliberately NOT the reference's
+ *                       _is_in_subgroup: that routine multiplies by the curve's cofactor constant instead of r
+ *                       (and reads 4 limbs of it), so it answers 0 for the subgroup generator of all four
+ *                       groups and 1 only at infinity, while its own scl_Fr_std(r, generator) is infinity.
+ *                       The definition here is [r]P = O with the reference's scalar multiplication as oracle.
+ * Return value: the number of rows that lack any of CANONICAL | ON_CURVE | IN_SUBGROUP (0: the batch is
+ * valid), counted on the device; flags may be NULL for the count alone.  -1 with nothing written for n < 0,
+ * an unknown curve or coords, or ZKG_COORDS_JAC on G2 (a return code: the error channel stays clear), and -1
+ * with the error channel set for a device error.  n == 0 returns 0.  Inputs are never written and nothing
+ * outside flag bytes [0, n) is; the calls are synchronous, thread-safe and run on the calling thread's
+ * device.  No data-dependent trip count: rows that are not points cost what points cost and nothing faults.
+ * zkg_check_set_mode (test hook): 0 the default membership chains (BN128 G1: cofactor 1, none; BLS12-381 G1:
+ * phi(P) == [z^2 - 1]P; BLS12-381 G2: psi(P) == [z]P; BN128 G2: [x + 1]P + psi([x]P) + psi^2([x]P) ==
+ * psi^3([2x]P)), 1 the exact chain [r]P everywhere (the definition), 2 the curve pass alone (a measurement
+ * hook: IN_SUBGROUP stays clear on finite rows, which therefore count as failing), < 0 restores the default.
+ * zkg_check_set_max_lanes (test hook, as zkg_g2_fft_set_max_lanes): lanes of the membership kernel, so that
+ * its grid-stride loop runs at small n; <= 0 restores the default. */
+#define ZKG_PT_CANONICAL 1
+#define ZKG_PT_ON_CURVE 2
+#define ZKG_PT_IN_SUBGROUP 4
+#define ZKG_PT_INFINITY 8
+#define ZKG_COORDS_AFFINE 0 /* 2 NP words */
+#define ZKG_COORDS_PROJ 1   /* 3 NP words */
+#define ZKG_COORDS_JAC 2    /* 3 NP words, G1 only */
+ZKG_API int zkg_g1_check_rows(int curve, int n, const uint64_t *pts, int coords, uint8_t *flags);
+ZKG_API int zkg_g1_check_rows_device(int curve, int n, const uint64_t *d_pts, int coords, uint8_t *d_flags);
+ZKG_API int zkg_g2_check_rows(int curve, int n, const uint64_t *pts, int coords, uint8_t *flags);
+ZKG_API int zkg_g2_check_rows_device(int curve, int n, const uint64_t *d_pts, int coords, uint8_t *d_flags);
+ZKG_API void zkg_check_set_mode(int mode);
+ZKG_API void zkg_check_set_max_lanes(int lanes);
 
 /* timing probe of the dominant kernel (MSM bucket accumulation / NTT pass chain),
  * measured with HIP events on each device's own stream; read sums over devices */

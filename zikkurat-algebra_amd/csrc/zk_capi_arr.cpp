@@ -467,3 +467,32 @@ ZKG_API int zkg_pairing_final_expo_device(int curve, int n, const uint64_t *d_sr
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------- batch point validation
+// <C>_G{1,2}_{affine,proj,jac}_is_on_curve / _is_infinity per row, and [r]P = O for membership
+#include "zk_check.hpp"
+
+namespace {
+// the refusals: a return code, before any device is opened
+bool check_args_ok(int curve, int n, int coords, bool g2) {
+  return n >= 0 && (curve == ZKG_BN128 || curve == ZKG_BLS12_381) &&
+         (coords == ZKG_COORDS_AFFINE || coords == ZKG_COORDS_PROJ || (coords == ZKG_COORDS_JAC && !g2));
+}
+}  // namespace
+
+extern "C" {
+
+#define ZKG_CHECK_ENTRY(NAME, FN, G2, HOST_IO)                                                  \
+  ZKG_API int NAME(int curve, int n, const uint64_t *pts, int coords, uint8_t *flags) {         \
+    if (!check_args_ok(curve, n, coords, G2)) return -1;                                        \
+    if (n == 0) return 0;                                                                       \
+    return guard_ret<int>(-1, [&] { return zk::FN(curve, n, pts, coords, flags, HOST_IO); });   \
+  }
+ZKG_CHECK_ENTRY(zkg_g1_check_rows, g1_check_rows, false, true)
+ZKG_CHECK_ENTRY(zkg_g1_check_rows_device, g1_check_rows, false, false)
+ZKG_CHECK_ENTRY(zkg_g2_check_rows, g2_check_rows, true, true)
+ZKG_CHECK_ENTRY(zkg_g2_check_rows_device, g2_check_rows, true, false)
+ZKG_API void zkg_check_set_mode(int mode) { zk::check_set_mode(mode); }
+ZKG_API void zkg_check_set_max_lanes(int lanes) { zk::check_set_max_lanes(lanes); }
+
+}  // extern "C"

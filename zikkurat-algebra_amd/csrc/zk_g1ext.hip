@@ -50,6 +50,7 @@
 #include "zk_extdev.hpp"
 #include "zk_fftdev.hpp"
 #include "zk_host.hpp"
+#include "zk_member.hpp"
 #include "zk_msm.hpp"
 #include "zk_runtime.hpp"
 #include "zk_g1ext.hpp"
@@ -762,22 +763,7 @@ __global__ void __launch_bounds__(256) k_fft_radix_sum(int m, int lgG, const uin
   if (j == 0) xyzz_store(B + o * xw<F>(), acc);  // = c' + G (k0 + q L)
 }
 
-// r = [|z|] p for BLS12-381's z = -0xd201000000010000 (bits 63, 62, 60, 57, 48, 16): 63 doublings
-// and 5 additions, the membership test's chain (k_subgroup_check)
-template <class F>
-__device__ __forceinline__ void jac_mul_absz(Jac<F> &r, const Jac<F> &p) {
-  JacC<F> pc;
-  jac_cache(pc, p);
-  r = p;
-  // runs of doublings between the set bits, each a rolled loop: the fully unrolled chain (63
-  // inlined doublings) held 512 VGPRs and spilled 230 of them to scratch
-  constexpr int kRun[6] = {1, 2, 3, 9, 32, 16};  // doublings before the additions at bits 62, 60, 57, 48, 16; tail
-  for (int s = 0; s < 6; s++) {
-#pragma unroll 1
-    for (int i = 0; i < kRun[s]; i++) jac_dbl(r);
-    if (s < 5 && !jac_is_inf(p)) jac_add_cached(r, pc);
-  }
-}
+// (jac_mul_absz, the membership test's [|z|] chain: zk_member.hpp, shared with zk_check*.hip)
 
 // subgroup membership (curves with a cofactor): phi(P) == [lambda] P for every point (lambda
 // 128 bits on BLS12-381; tools/gen_glv.py checks the test on subgroup and non-subgroup points).

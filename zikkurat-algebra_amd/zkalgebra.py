@@ -95,6 +95,12 @@ EXTENSION_SYMBOLS += [f"zkg_g2_scl_{k}{d}" for k in ("fixed", "rows", "powers") 
 # pairings: the reference's single-pair symbols, and the batch / product / final-exponentiation extensions
 REFERENCE_SYMBOLS += [f"{c}_pairing_{k}" for c in CURVES for k in ("affine", "projective")]
 EXTENSION_SYMBOLS += [f"zkg_pairing_{k}{d}" for k in ("rows", "product", "final_expo") for d in ("", "_device")]
+# batch point validation: canonical / on-curve / subgroup / infinity flags per row, and its test hooks
+EXTENSION_SYMBOLS += [f"zkg_g{g}_check_rows{d}" for g in (1, 2) for d in ("", "_device")] + [
+    "zkg_check_set_mode", "zkg_check_set_max_lanes"]
+PT_CANONICAL, PT_ON_CURVE, PT_IN_SUBGROUP, PT_INFINITY = 1, 2, 4, 8
+PT_VALID = PT_CANONICAL | PT_ON_CURVE | PT_IN_SUBGROUP
+COORDS_ID = {"affine": 0, "proj": 1, "jac": 2}
 
 _lib = None
 
@@ -216,6 +222,15 @@ def load():
             lib.zkg_g2_scl_set_fixed_min.argtypes = [ctypes.c_int]
             lib.zkg_g2_scl_table_bytes.restype = ctypes.c_size_t
             lib.zkg_g2_scl_table_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+        if hasattr(lib, "zkg_g1_check_rows"):  # absent from an older variant build, as above
+            for g in (1, 2):
+                for d in ("", "_device"):
+                    getattr(lib, f"zkg_g{g}_check_rows{d}").argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                                        ctypes.c_int, ctypes.c_void_p]
+            lib.zkg_check_set_mode.argtypes = [ctypes.c_int]
+            lib.zkg_check_set_mode.restype = None
+            lib.zkg_check_set_max_lanes.argtypes = [ctypes.c_int]
+            lib.zkg_check_set_max_lanes.restype = None
         lib.zkg_last_error.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         lib.zkg_comm_unique_id.argtypes = [ctypes.c_void_p]
         lib.zkg_comm_init.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
@@ -1376,11 +1391,13 @@ def _g1_neg_proj(curve, pt):
     return out
 
 
-def kzg_verify(curve, g1, g2, tau_g2, commitment, x0, y0, proof):
+def kzg_verify(curve, g1, g2, tau_g2, commitment, x0, y0, proof, validate=False):
     """verifyProof (examples/KZG.hs:120-124): pairing(proof, tau g2) == pairing(point, g2) with
     point = commitment + [x0] proof - [y0] g1, evaluated as the two-row product
     pairing(proof, tau g2) pairing(-point, g2) == 1.  g1 affine G1, g2 / tau_g2 affine G2, commitment and
-    proof projective G1 rows (what msm returns), x0 / y0 Montgomery Fr."""
+    proof projective G1 rows (what msm returns), x0 / y0 Montgomery Fr.  validate: the commitment, the proof
+    and tau_g2 are checked first (g1_all_valid / g2_all_valid: canonical, on the curve, in the subgroup) and
+    an invalid point returns False; without it nothing is checked, as before."""
     NP = NLIMBS_P[curve]
     g1 = _g1_aff(curve, g1, "kzg_verify")
     g2 = np.ascontiguousarray(g2, dtype=np.uint64).reshape(-1)
@@ -1391,12 +1408,163 @@ def kzg_verify(curve, g1, g2, tau_g2, commitment, x0, y0, proof):
         raise ValueError("kzg_verify: incompatible array dimensions")
     x0, y0 = _k(x0), _k(y0)
     require_gpu()
+    if validate and not (g1_all_valid(curve, np.stack([commitment, proof]), coords="proj")
+                         and g2_all_valid(curve, tau_g2.reshape(1, -1))):
+        return False
     proof_aff = g1_to_affine(curve, proof)
     xq = scalar_mul_rows(curve, x0.reshape(1, 4), proof_aff.reshape(1, -1))[0]
     yg = scalar_mul_fixed(curve, y0.reshape(1, 4), g1)[0]
     point = g1_add(curve, g1_add(curve, commitment, xq), _g1_neg_proj(curve, yg))
     neg_aff = g1_to_affine(curve, _g1_neg_proj(curve, point))
     return pairing_check(curve, np.stack([proof_aff, neg_aff]), np.stack([tau_g2, g2]))
+
+
+# ---------------------------------------------------------------------------- point validation
+# zkg_g{1,2}_check_rows: per row PT_CANONICAL | PT_ON_CURVE | PT_IN_SUBGROUP | PT_INFINITY.  ON_CURVE and
+# INFINITY are the reference's <C>_G{1,2}_{affine,proj,jac}_is_on_curve / _is_infinity; IN_SUBGROUP is
+# [r]P = O, not the reference's _is_in_subgroup (which multiplies by the cofactor and rejects the generator).
+
+def _check_rows(curve, pts, coords, group, name):
+    """(rows, coords id) of a G1 (group 1) or G2 (group 2) point array in coordinate system `coords`"""
+    if coords not in COORDS_ID or (group == 2 and coords == "jac"):
+        raise ValueError(f"{name}: coords must be 'affine', 'proj'" + (" or 'jac'" if group == 1 else ""))
+    pts = np.ascontiguousarray(pts, dtype=np.uint64)
+    words = (2 if coords == "affine" else 3) * group * NLIMBS_P[curve]
+    if pts.ndim != 2 or pts.shape[1] != words:
+        raise ValueError(f"{name}: incompatible array dimensions ({coords} rows have {words} words)")
+    return pts, COORDS_ID[coords]
+
+
+def _check_rc(rc, name):
+    if rc < 0:
+        raise ValueError(f"{name}: the call was refused ({last_error() or 'bad arguments'})")
+    return rc
+
+
+def _check_host(curve, pts, coords, group, name, want_flags):
+    pts, cid = _check_rows(curve, pts, coords, group, name)
+    require_gpu()
+    flags = np.zeros(pts.shape[0], dtype=np.uint8) if want_flags else None
+    f = getattr(load(), f"zkg_g{group}_check_rows")
+    rc = _check_rc(f(CURVE_ID[curve], pts.shape[0], pts.ctypes.data, cid, flags.ctypes.data if want_flags else None),
+                   name)
+    return flags if want_flags else rc
+
+
+def g1_check(curve, pts, coords="affine"):
+    """one flag byte per G1 row (PT_*): affine rows of 2 NP words, 'proj' / 'jac' rows of 3 NP words"""
+    return _check_host(curve, pts, coords, 1, "g1_check", True)
+
+
+def g2_check(curve, pts, coords="affine"):
+    """one flag byte per G2 row (PT_*): affine rows of 4 NP words, 'proj' rows of 6 NP words"""
+    return _check_host(curve, pts, coords, 2, "g2_check", True)
+
+
+def g1_all_valid(curve, pts, coords="affine"):
+    """every row is canonical, on the curve and in the order-r subgroup (the count-only call; infinity passes)"""
+    return _check_host(curve, pts, coords, 1, "g1_all_valid", False) == 0
+
+
+def g2_all_valid(curve, pts, coords="affine"):
+    return _check_host(curve, pts, coords, 2, "g2_all_valid", False) == 0
+
+
+def _check_device(curve, n, d_pts, coords, d_flags, group, name):
+    if coords not in COORDS_ID or (group == 2 and coords == "jac"):
+        raise ValueError(f"{name}: coords must be 'affine', 'proj'" + (" or 'jac'" if group == 1 else ""))
+    f = getattr(load(), f"zkg_g{group}_check_rows_device")
+    return f(CURVE_ID[curve], n, d_pts.ptr if d_pts else None, COORDS_ID[coords], d_flags.ptr if d_flags else None)
+
+
+def g1_check_device(curve, n, d_pts, d_flags=None, coords="affine"):
+    """device-resident g1_check (zkg_g1_check_rows_device): n flag bytes into d_flags (None: the count alone);
+    returns the number of invalid rows, or -1"""
+    return _check_device(curve, n, d_pts, coords, d_flags, 1, "g1_check_device")
+
+
+def g2_check_device(curve, n, d_pts, d_flags=None, coords="affine"):
+    """device-resident g2_check (zkg_g2_check_rows_device)"""
+    return _check_device(curve, n, d_pts, coords, d_flags, 2, "g2_check_device")
+
+
+def check_set_mode(mode):
+    """test hook: 0 the default membership chains, 1 the exact chain [r]P everywhere, 2 the curve pass alone
+    (measurement: finite rows then count as failing), < 0 restores the default"""
+    load().zkg_check_set_mode(int(mode))
+
+
+def check_set_max_lanes(lanes):
+    """test hook: lanes of the membership kernel (its grid-stride loop at small n); <= 0 restores the default"""
+    load().zkg_check_set_max_lanes(int(lanes))
+
+
+@dataclass
+class SRSCheck:
+    """result of srs_check: ok, or the first failed stage ("points", "g1 powers", "g2 powers")"""
+    ok: bool
+    failed: str = None
+
+    def __bool__(self):
+        return self.ok
+
+
+def _fr_mont(curve, v):
+    """the Montgomery words of the integer v mod r"""
+    r = FR_ORDER[curve]
+    v = (v % r) * (1 << 256) % r
+    return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+
+
+FR_ORDER = {
+    "bn128": 0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001,
+    "bls12_381": 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
+}
+
+
+def srs_check(curve, g1_powers, g2_powers, rho=None):
+    """Is (P_0 .. P_{n-1}; Q_0 .. Q_{k-1}) a powers-of-tau SRS, P_i = [tau^i] P_0 and Q_j = [tau^j] Q_0?  What a
+    prover runs on a ceremony file before it commits with it.  g1_powers: n affine (2 NP words) or projective
+    (3 NP) G1 rows; g2_powers: k >= 2 affine (4 NP) or projective (6 NP) G2 rows; rho: the random challenge, an
+    integer (default: drawn with `secrets`).
+      "points"     every row of both columns is canonical, on its curve, in the subgroup and not infinity
+      "g1 powers"  e(sum rho^i P_i, Q_1) == e(sum rho^i P_{i+1}, Q_0) over i < n - 1 (two MSMs, one pairing product)
+      "g2 powers"  with k > 2: e(P_1, sum rho^j Q_j) == e(P_0, sum rho^j Q_{j+1}) over j < k - 1
+    Returns SRSCheck(ok, failed): truthy on success, else `failed` names the first stage that did not hold."""
+    NP = NLIMBS_P[curve]
+    g1_powers = np.ascontiguousarray(g1_powers, dtype=np.uint64)
+    g2_powers = np.ascontiguousarray(g2_powers, dtype=np.uint64)
+    if g1_powers.ndim != 2 or g1_powers.shape[1] not in (2 * NP, 3 * NP) or g1_powers.shape[0] < 1:
+        raise ValueError("srs_check: g1_powers must be affine or projective G1 rows")
+    if g2_powers.ndim != 2 or g2_powers.shape[1] not in (4 * NP, 6 * NP) or g2_powers.shape[0] < 2:
+        raise ValueError("srs_check: g2_powers must be at least two affine or projective G2 rows")
+    c1 = "affine" if g1_powers.shape[1] == 2 * NP else "proj"
+    c2 = "affine" if g2_powers.shape[1] == 4 * NP else "proj"
+    require_gpu()
+    for flags in (g1_check(curve, g1_powers, c1), g2_check(curve, g2_powers, c2)):
+        if np.any((flags & PT_VALID) != PT_VALID) or np.any(flags & PT_INFINITY):
+            return SRSCheck(False, "points")
+    if rho is None:
+        import secrets
+        rho = secrets.randbelow(FR_ORDER[curve] - 2) + 2
+    P = g1_powers if c1 == "affine" else batch_to_affine(curve, g1_powers)
+    Q = g2_powers if c2 == "affine" else g2_batch_to_affine(curve, g2_powers)
+    n, k = P.shape[0], Q.shape[0]
+    pw = arr_powers(curve, _fr_mont(curve, 1), _fr_mont(curve, rho), max(n, k) - 1) if max(n, k) > 1 else None
+
+    def neg1(aff):  # -(x, y) of an affine G1 row (all-0xFF stays infinity)
+        return g1_to_affine(curve, _g1_neg_proj(curve, batch_from_affine(curve, aff.reshape(1, -1))[0]))
+    if n > 1:
+        a = msm_affine(curve, pw[:n - 1], np.ascontiguousarray(P[:n - 1]))
+        b = msm_affine(curve, pw[:n - 1], np.ascontiguousarray(P[1:]))
+        if not pairing_check(curve, np.stack([a, neg1(b)]), np.stack([Q[1], Q[0]])):
+            return SRSCheck(False, "g1 powers")
+    if k > 2 and n > 1:
+        sa = g2_msm(curve, pw[:k - 1], np.ascontiguousarray(Q[:k - 1]), affine=True)
+        sb = g2_msm(curve, pw[:k - 1], np.ascontiguousarray(Q[1:]), affine=True)
+        if not pairing_check(curve, np.stack([P[1], neg1(P[0])]), np.stack([sa, sb])):
+            return SRSCheck(False, "g2 powers")
+    return SRSCheck(True)
 
 
 def poly_mul_device(curve, n1, d_a, n2, d_b, d_tgt):
