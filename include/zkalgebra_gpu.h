@@ -428,6 +428,42 @@ ZKG_API int  zkg_poly_last_div_steps(void);
 ZKG_API void zkg_poly_div_profile(int on);
 ZKG_API void zkg_poly_last_div_phase_ms(double *ms);
 
+/* Division by a linear factor x - z, for nz points at once: what <C>_poly_mont_div_by_vanishing computes
+ * with expo_n = 1 (bls12_381_poly_mont.c:317-397; examples/KZG.hs openingProof), every word bit-identical
+ * to it for canonical Montgomery inputs.  z: HOST, nz x 4 words.  For point k, quot rows
+ * [k (n - 1), (k + 1)(n - 1)) receive the n - 1 quotient coefficients (zero rows above the quotient's
+ * degree, as the reference's cleared tail) and vals[k] (HOST, nz x 4 words) receives p(z_k), the
+ * remainder.  quot may be NULL: the values alone.  n = 1 writes no quotient and the value a_0; n = 0 the
+ * value 0.  A tiled suffix scan in three launches (zk_lindiv.hip): two reads and one write of the
+ * coefficients per point.  Return 0, or -1 with nothing written and the text in zkg_last_error (in either
+ * error mode) for an unknown curve, a negative size, NULL where a pointer is required, or a quotient
+ * buffer that overlaps the polynomial: the write pass stores across tile boundaries, so aliasing would be
+ * a race.  A device error goes through the error channel as everywhere.  Synchronous and thread-safe, on the
+ * calling thread's device. */
+ZKG_API int zkg_poly_div_linear_device(int curve, int n, const uint64_t *d_poly, int nz, const uint64_t *z,
+                                       uint64_t *d_quot, uint64_t *vals);                 /* DEVICE poly, quot */
+ZKG_API int zkg_poly_div_linear(int curve, int n, const uint64_t *poly, int nz, const uint64_t *z, uint64_t *quot,
+                                uint64_t *vals);                                          /* HOST pointers */
+/* test hook: rows per lane of a tile of the scan (a tile is 256 lanes x rows), so that a few thousand
+ * coefficients span many tiles and several iterations of the carry pass; the kernels exist for 1, 2, 4 and 8
+ * (the default) rows: 0 restores the default, larger values are clamped to it, 3 counts as 2 and 5 .. 7 as 4.
+ * zkg_poly_lindiv_tile: the value in force.  The results do not depend on it. */
+ZKG_API void zkg_poly_set_lindiv_tile(int rows_per_lane);
+ZKG_API int  zkg_poly_lindiv_tile(void);
+
+/* KZG prover on a device-resident polynomial (n Montgomery Fr rows) and SRS (affine G1 rows, 2 NP words:
+ * what zkg_g1_batch_to_affine_device makes of a setup's projective rows); examples/KZG.hs commitPoly and
+ * openingProof.  commit: tgt_proj (HOST, 3 NP words) = the normalised projective sum of coeffs_i srs_i,
+ * i < n: zkg_g1_msm_device with Montgomery coefficients.  open: for every point z_k (HOST, nz x 4 words),
+ * vals[k] = p(z_k) and proofs_proj row k (HOST, 3 NP words, normalised; (0 : 1 : 0) for n <= 1) = the
+ * commitment to the quotient of p by x - z_k against the first n - 1 SRS rows -- per point, the division
+ * above into a buffer of the call, then the device MSM, on the same stream.  Return codes and refusals as
+ * for zkg_poly_div_linear. */
+ZKG_API int zkg_kzg_commit_device(int curve, int n, const uint64_t *d_coeffs, const uint64_t *d_srs_affine,
+                                  uint64_t *tgt_proj);
+ZKG_API int zkg_kzg_open_device(int curve, int n, const uint64_t *d_poly, const uint64_t *d_srs_affine, int nz,
+                                const uint64_t *z, uint64_t *vals, uint64_t *proofs_proj);
+
 
 /* device-resident G1 group FFT / batch_to_affine (d_* DEVICE pointers, gen on the host) */
 ZKG_API void zkg_g1_fft_device(int curve, int inverse, int m, const uint64_t *gen, const uint64_t *d_src,

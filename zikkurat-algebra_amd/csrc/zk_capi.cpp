@@ -219,6 +219,72 @@ ZKG_API void zkg_g2_msm_device(int curve, int npoints, const uint64_t *d_expos, 
   });
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------------------- KZG prover
+// examples/KZG.hs commitPoly (msm coeffs tauG1s) and openingProof (quotByVanishing (p - val) (1, loc), then
+// commitPoly of the quotient) on a device-resident polynomial and SRS
+#include "zk_lindiv.hpp"
+
+namespace {
+int kzg_refuse(const char *msg) {
+  zk::record_error(msg);
+  return -1;
+}
+// the normalised projective sum of n Montgomery coefficients against n affine rows, all on the device
+void kzg_msm(int curve, int n, const uint64_t *d_coeffs, const uint64_t *d_srs_affine, uint64_t *tgt_proj) {
+  uint64_t p[18];
+  if (curve == ZKG_BN128) msm_g1<BN254>(n, d_coeffs, 4, d_srs_affine, false, true, 0, p);
+  else msm_g1<BLS381>(n, d_coeffs, 4, d_srs_affine, false, true, 0, p);
+  zkg_g1_proj_normalize(curve, p, tgt_proj);
+}
+// device rows that live as long as the scope (also while a zk::Error unwinds it)
+struct DeviceRows {
+  uint64_t *p = nullptr;
+  explicit DeviceRows(size_t rows) {
+    if (rows) ZK_CHECK(hipMalloc(reinterpret_cast<void **>(&p), rows * 32));
+  }
+  DeviceRows(const DeviceRows &) = delete;
+  DeviceRows &operator=(const DeviceRows &) = delete;
+  ~DeviceRows() {
+    if (p && hipFree(p) != hipSuccess) (void)hipGetLastError();
+  }
+};
+}  // namespace
+
+extern "C" {
+
+ZKG_API int zkg_kzg_commit_device(int curve, int n, const uint64_t *d_coeffs, const uint64_t *d_srs_affine,
+                                  uint64_t *tgt_proj) {
+  if (curve != ZKG_BN128 && curve != ZKG_BLS12_381) return kzg_refuse("kzg_commit: unknown curve");
+  if (n < 0) return kzg_refuse("kzg_commit: negative size");
+  if (!tgt_proj || (n > 0 && (!d_coeffs || !d_srs_affine))) return kzg_refuse("kzg_commit: null buffer");
+  return guard_ret<int>(-1, [&] {
+    kzg_msm(curve, n, d_coeffs, d_srs_affine, tgt_proj);
+    return 0;
+  });
+}
+
+ZKG_API int zkg_kzg_open_device(int curve, int n, const uint64_t *d_poly, const uint64_t *d_srs_affine, int nz,
+                                const uint64_t *z, uint64_t *vals, uint64_t *proofs_proj) {
+  if (curve != ZKG_BN128 && curve != ZKG_BLS12_381) return kzg_refuse("kzg_open: unknown curve");
+  if (n < 0 || nz < 0) return kzg_refuse("kzg_open: negative size");
+  if (nz > 0 && (!z || !vals || !proofs_proj)) return kzg_refuse("kzg_open: null points, values or proofs");
+  if (nz > 0 && ((n > 0 && !d_poly) || (n > 1 && !d_srs_affine))) return kzg_refuse("kzg_open: null buffer");
+  return guard_ret<int>(-1, [&] {
+    // The quotient rows of one point at a time.  They are a buffer of this call, not rows of the arena: the
+    // MSM that follows resets the arena and may move it.
+    const int nq = n > 1 ? n - 1 : 0;
+    const int NP = curve == ZKG_BN128 ? 4 : 6;
+    DeviceRows quot((size_t)nq);
+    for (int k = 0; k < nz; k++) {
+      zk::poly_div_linear(curve, n, d_poly, 1, z + 4 * (size_t)k, quot.p, vals + 4 * (size_t)k, false);
+      kzg_msm(curve, nq, quot.p, d_srs_affine, proofs_proj + (size_t)k * 3 * NP);
+    }
+    return 0;
+  });
+}
+
 ZKG_API void zkg_ntt_device(int curve, int inverse, int m, const uint64_t *gen, const uint64_t *d_src,
                             uint64_t *d_tgt) {
   guard([&] { zk::ntt(curve, m, gen, d_src, d_tgt, false, inverse != 0); });

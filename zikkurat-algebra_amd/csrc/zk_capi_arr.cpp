@@ -260,6 +260,49 @@ ZKG_API int zkg_poly_last_mul_path(void) { return zk::poly_last_mul_path(); }
 
 }  // extern "C"
 
+// ---------------------------------------------------------------------------- division by x - z
+// <C>_poly_mont_div_by_vanishing with expo_n = 1 (bls12_381_poly_mont.c:317-397), many points at once
+#include "zk_lindiv.hpp"
+
+namespace {
+// a refusal: the message on the calling thread's error channel and a nonzero code, in either error mode
+int refuse(const char *msg) {
+  zk::record_error(msg);
+  return -1;
+}
+int div_linear_g(int curve, int n, const uint64_t *poly, int nz, const uint64_t *z, uint64_t *quot, uint64_t *vals,
+                 bool host_io) {
+  if (curve != ZKG_BN128 && curve != ZKG_BLS12_381) return refuse("poly_div_linear: unknown curve");
+  if (n < 0 || nz < 0) return refuse("poly_div_linear: negative size");
+  if (nz > 0 && (!z || !vals)) return refuse("poly_div_linear: null points or values");
+  if (nz > 0 && n > 0 && !poly) return refuse("poly_div_linear: null polynomial");
+  if (quot && n > 1 && nz > 0) {  // the write pass stores across tile boundaries: aliasing is a race
+    const uintptr_t p0 = (uintptr_t)poly, p1 = p0 + (size_t)n * 32;
+    const uintptr_t q0 = (uintptr_t)quot, q1 = q0 + (size_t)nz * ((size_t)n - 1) * 32;
+    if (p0 < q1 && q0 < p1) return refuse("poly_div_linear: the quotient overlaps the polynomial");
+  }
+  return guard_ret<int>(-1, [&] {
+    zk::poly_div_linear(curve, n, poly, nz, z, quot, vals, host_io);
+    return 0;
+  });
+}
+}  // namespace
+
+extern "C" {
+
+ZKG_API int zkg_poly_div_linear_device(int curve, int n, const uint64_t *d_poly, int nz, const uint64_t *z,
+                                       uint64_t *d_quot, uint64_t *vals) {
+  return div_linear_g(curve, n, d_poly, nz, z, d_quot, vals, false);
+}
+ZKG_API int zkg_poly_div_linear(int curve, int n, const uint64_t *poly, int nz, const uint64_t *z, uint64_t *quot,
+                                uint64_t *vals) {
+  return div_linear_g(curve, n, poly, nz, z, quot, vals, true);
+}
+ZKG_API void zkg_poly_set_lindiv_tile(int rows_per_lane) { zk::poly_set_lindiv_tile(rows_per_lane); }
+ZKG_API int zkg_poly_lindiv_tile(void) { return zk::poly_lindiv_tile(); }
+
+}  // extern "C"
+
 // ---------------------------------------------------------------------------- G1
 #include "zk_g1ext.hpp"
 

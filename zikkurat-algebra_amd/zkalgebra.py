@@ -98,6 +98,9 @@ EXTENSION_SYMBOLS += [f"zkg_pairing_{k}{d}" for k in ("rows", "product", "final_
 # batch point validation: canonical / on-curve / subgroup / infinity flags per row, and its test hooks
 EXTENSION_SYMBOLS += [f"zkg_g{g}_check_rows{d}" for g in (1, 2) for d in ("", "_device")] + [
     "zkg_check_set_mode", "zkg_check_set_max_lanes"]
+# division by a linear factor, and the KZG prover on it
+EXTENSION_SYMBOLS += ["zkg_poly_div_linear_device", "zkg_poly_div_linear", "zkg_poly_set_lindiv_tile",
+                      "zkg_poly_lindiv_tile", "zkg_kzg_commit_device", "zkg_kzg_open_device"]
 PT_CANONICAL, PT_ON_CURVE, PT_IN_SUBGROUP, PT_INFINITY = 1, 2, 4, 8
 PT_VALID = PT_CANONICAL | PT_ON_CURVE | PT_IN_SUBGROUP
 COORDS_ID = {"affine": 0, "proj": 1, "jac": 2}
@@ -231,6 +234,14 @@ def load():
             lib.zkg_check_set_mode.restype = None
             lib.zkg_check_set_max_lanes.argtypes = [ctypes.c_int]
             lib.zkg_check_set_max_lanes.restype = None
+        if hasattr(lib, "zkg_poly_div_linear"):  # absent from an older variant build, as above
+            vp = ctypes.c_void_p
+            for f in (lib.zkg_poly_div_linear_device, lib.zkg_poly_div_linear):
+                f.argtypes = [ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp]
+            lib.zkg_poly_set_lindiv_tile.argtypes = [ctypes.c_int]
+            lib.zkg_poly_set_lindiv_tile.restype = None
+            lib.zkg_kzg_commit_device.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp]
+            lib.zkg_kzg_open_device.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp]
         lib.zkg_last_error.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         lib.zkg_comm_unique_id.argtypes = [ctypes.c_void_p]
         lib.zkg_comm_init.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
@@ -1238,18 +1249,38 @@ def g2_scl_table_bytes(curve, c):
 @dataclass
 class KZGSetup:
     """Mirror of examples/KZG.hs KZGSetup: the point arrays stay on the device (projective rows);
-    tau_g2s ([tau^i] g2, i < g2_powers) only when kzg_setup was asked for it"""
+    tau_g2s ([tau^i] g2, i < g2_powers) only when kzg_setup was asked for it.  The affine rows the MSM
+    takes are made from the projective ones on first use (affine_rows) and kept until free()."""
     domain: FFTSubgroup
     tau_g1s: "DeviceBuffer"
     lagrange_taus: "DeviceBuffer"
     g2_tau_g2: tuple
     tau_g2s: "DeviceBuffer" = None
+    _affine: dict = None
+
+    def affine_rows(self, which):
+        """the device buffer of affine rows of `which` ('tau_g1s' or 'lagrange_taus'), made once"""
+        if self._affine is None:
+            self._affine = {}
+        if which not in self._affine:
+            curve, n = self.domain.curve, self.domain.size
+            buf = DeviceBuffer.empty(n * 2 * NLIMBS_P[curve] * 8)
+            try:
+                batch_to_affine_device(curve, n, getattr(self, which), buf)
+            except Exception:
+                buf.free()
+                raise
+            self._affine[which] = buf
+        return self._affine[which]
 
     def free(self):
         self.tau_g1s.free()
         self.lagrange_taus.free()
         if self.tau_g2s is not None:
             self.tau_g2s.free()
+        for b in (self._affine or {}).values():
+            b.free()
+        self._affine = None
 
 
 def kzg_setup(curve, tau, log_size, g1, g2, g2_powers=0):
@@ -1278,6 +1309,134 @@ def kzg_setup(curve, tau, log_size, g1, g2, g2_powers=0):
             b.free()
         raise
     return KZGSetup(dom, taus, lag, (g2.reshape(-1), tau_g2), tau_g2s)
+
+
+# ---------------------------------------------------------------------------- KZG prover
+# division by x - z (zk_lindiv.hip) and examples/KZG.hs commitPoly / commitValues / commitInterpolate / openingProof
+
+def _lindiv_rc(rc, name):
+    if rc != 0:
+        raise ValueError(f"{name}: the call was refused ({last_error() or 'bad arguments'})")
+
+
+def _points(z):
+    """(rows (nz, 4), single) of one point or an (nz, 4) array of points"""
+    z = np.ascontiguousarray(z, dtype=np.uint64)
+    single = z.ndim == 1
+    rows = z.reshape(1, -1) if single else z
+    if rows.ndim != 2 or rows.shape[1] != NLIMBS_R:
+        raise TypeError("a point is one Fr element (4 words), or an (nz, 4) array of them")
+    return rows, single
+
+
+def poly_div_linear(curve, poly, z):
+    """the quotient of poly by x - z and the value poly(z), what quot_by_vanishing(poly - val, 1, z) and
+    poly_eval_at give, in one sweep (zkg_poly_div_linear).  One point: (quot (n - 1, 4), val (4,)); an (nz, 4)
+    array of points: (quot (nz, n - 1, 4), vals (nz, 4)).  n - 1 rows always (zero above the quotient's degree)."""
+    poly = _fr(poly)
+    zs, single = _points(z)
+    n, nz = poly.shape[0], zs.shape[0]
+    require_gpu()
+    quot = np.zeros((nz, max(0, n - 1), 4), dtype=np.uint64)
+    vals = np.zeros((nz, 4), dtype=np.uint64)
+    _lindiv_rc(load().zkg_poly_div_linear(CURVE_ID[curve], n, poly.ctypes.data, nz, zs.ctypes.data, quot.ctypes.data,
+                                          vals.ctypes.data), "poly_div_linear")
+    return (quot[0], vals[0]) if single else (quot, vals)
+
+
+def poly_div_linear_device(curve, n, d_poly, z, d_quot=None):
+    """device-resident poly_div_linear (zkg_poly_div_linear_device): d_quot receives nz x (n - 1) rows (None:
+    the values alone) and does not overlap d_poly; returns (rc, vals (nz, 4)), rc nonzero for a refused call
+    (last_error() has the text)"""
+    zs, _ = _points(z)
+    vals = np.zeros((zs.shape[0], 4), dtype=np.uint64)
+    rc = load().zkg_poly_div_linear_device(CURVE_ID[curve], n, d_poly.ptr if d_poly else None, zs.shape[0],
+                                           zs.ctypes.data, d_quot.ptr if d_quot else None, vals.ctypes.data)
+    return rc, vals
+
+
+def poly_set_lindiv_tile(rows_per_lane):
+    """test hook: rows per lane of a tile of the division's scan (1, 2, 4 or 8; 0 restores the default)"""
+    load().zkg_poly_set_lindiv_tile(int(rows_per_lane))
+
+
+def poly_lindiv_tile():
+    """rows per lane in force: a tile is 256 times as many rows"""
+    return load().zkg_poly_lindiv_tile()
+
+
+def _g1_out(curve, proj, affine):
+    return g1_to_affine(curve, proj) if affine else proj
+
+
+def _kzg_commit(setup, coeffs, which, name, affine):
+    curve = setup.domain.curve
+    n = coeffs.shape[0]
+    require_gpu()
+    d_c = DeviceBuffer(coeffs)
+    try:
+        out = np.zeros(3 * NLIMBS_P[curve], dtype=np.uint64)
+        _lindiv_rc(load().zkg_kzg_commit_device(CURVE_ID[curve], n, d_c.ptr, setup.affine_rows(which).ptr,
+                                                out.ctypes.data), name)
+    finally:
+        d_c.free()
+    return _g1_out(curve, out, affine)
+
+
+def kzg_commit(setup, poly, affine=False):
+    """commitPoly (examples/KZG.hs:85-89): msm of the coefficients against the first len(poly) rows of tauG1s;
+    the normalised projective row, or the affine one"""
+    poly = _fr(poly)
+    if poly.shape[0] > setup.domain.size:
+        raise ValueError("kzg_commit: the polynomial is longer than the KZG setup")
+    return _kzg_commit(setup, poly, "tau_g1s", "kzg_commit", affine)
+
+
+def kzg_commit_values(setup, values, affine=False):
+    """commitValues (examples/KZG.hs:91-98): msm of the values against lagrangeTaus"""
+    values = _fr(values)
+    if values.shape[0] != setup.domain.size:
+        raise ValueError("commitValues: expecting a vector of the same size as the KZG setup domain")
+    return _kzg_commit(setup, values, "lagrange_taus", "kzg_commit_values", affine)
+
+
+def kzg_commit_interpolate(setup, values, affine=False):
+    """commitInterpolate (examples/KZG.hs:100-107): commitPoly of the interpolated polynomial"""
+    values = _fr(values)
+    if values.shape[0] != setup.domain.size:
+        raise ValueError("commitInterpolate: expecting a vector of the same size as the KZG setup domain")
+    return kzg_commit(setup, inverse_ntt(setup.domain, values), affine=affine)
+
+
+def kzg_open_many(setup, poly, zs, affine=False):
+    """openingProof at every row of zs (nz, 4): (vals (nz, 4), proofs (nz, 3 NP) normalised projective, or
+    (nz, 2 NP) affine) -- zkg_kzg_open_device: per point the division by x - z, then the device MSM"""
+    poly = _fr(poly)
+    zs, _ = _points(zs)
+    curve, n, nz = setup.domain.curve, poly.shape[0], zs.shape[0]
+    if n > setup.domain.size:
+        raise ValueError("kzg_open: the polynomial is longer than the KZG setup")
+    require_gpu()
+    NP = NLIMBS_P[curve]
+    vals = np.zeros((nz, 4), dtype=np.uint64)
+    proofs = np.zeros((nz, 3 * NP), dtype=np.uint64)
+    d_p = DeviceBuffer(poly)
+    try:
+        _lindiv_rc(load().zkg_kzg_open_device(CURVE_ID[curve], n, d_p.ptr, setup.affine_rows("tau_g1s").ptr, nz,
+                                              zs.ctypes.data, vals.ctypes.data, proofs.ctypes.data), "kzg_open")
+    finally:
+        d_p.free()
+    if affine:
+        proofs = np.stack([g1_to_affine(curve, p) for p in proofs]) if nz else np.zeros((0, 2 * NP), dtype=np.uint64)
+    return vals, proofs
+
+
+def kzg_open(setup, poly, z, affine=False):
+    """openingProof (examples/KZG.hs:120-127): (z, val, proof) with val = poly(z) and proof the commitment to
+    (poly - val) / (x - z); a polynomial of length <= 1 gives the point at infinity"""
+    z = _k(z)
+    vals, proofs = kzg_open_many(setup, poly, z.reshape(1, 4), affine=affine)
+    return z, vals[0], proofs[0]
 
 
 # ---------------------------------------------------------------------------- pairings
