@@ -688,6 +688,36 @@ ZKG_API int zkg_g2_check_rows_device(int curve, int n, const uint64_t *d_pts, in
 ZKG_API void zkg_check_set_mode(int mode);
 ZKG_API void zkg_check_set_max_lanes(int lanes);
 
+/* Row-wise sum of scalar multiples: tgt[i] = sum_(j < terms) [k_(j,i)] P_(j,i), i < rows.  Term-major layout:
+ * term j's rows lie at j * rows + i in `expos` (4 words each) and `bases` (affine rows, 2 NP words, all-0xFF =
+ * infinity).  The contract of zkg_g1_scl_rows holds per product (expos_mont: Montgomery Fr brought to its
+ * canonical integer, otherwise raw 256-bit integers; no reduction mod r).  Equal terms, opposite terms and
+ * infinities are ordinary inputs; terms = 0 gives rows of infinity.  tgt: `rows` normalised projective rows
+ * (3 NP words), or affine rows (affine_out).  Returns 0, or -1 with the error channel set and nothing written:
+ * unknown curve, negative size, rows * terms >= 2^31, null buffer, tgt overlapping an input, device error. */
+ZKG_API int zkg_g1_scl_rows_sum_device(int curve, int rows, int terms, const uint64_t *d_expos, int expos_mont,
+                                       const uint64_t *d_bases, int affine_out, uint64_t *d_tgt);
+ZKG_API int zkg_g1_scl_rows_sum(int curve, int rows, int terms, const uint64_t *expos, int expos_mont,
+                                const uint64_t *bases, int affine_out, uint64_t *tgt);
+
+/* Every KZG opening of a domain at once (Feist-Khovratovich).  n = 2^log_n, l = 2^log_l (0 <= log_l <=
+ * log_n - 1), r = n / l, omega the generator of zkg_fft_generator(curve, log_n), psi = omega^l.  Proof k < r is
+ * the commitment to the quotient of the polynomial by x^l - psi^k: it opens the coset omega^k <omega^r>, and
+ * for l = 1 it is the proof of zkg_kzg_open_device at omega^k.
+ *   zkg_kzg_open_all_table_bytes   bytes of the table of (log_n, log_l): 2 n affine rows (0 for a refused shape)
+ *   zkg_kzg_open_all_table_device  builds it from d_srs_affine, the first n affine rows [tau^i] g1: l group
+ *                                  FFTs of size 2 r, term-major; once per setup and (log_n, log_l)
+ *   zkg_kzg_open_all_device        d_poly: npoly <= n Montgomery coefficients (zero-extended); d_proofs: r
+ *                                  normalised projective rows, or affine (affine_out)
+ * Return 0, or -1 with the error channel set and nothing written: unknown curve, log_n outside 1..28, log_l
+ * outside 0..log_n - 1, a 2 r domain beyond the field's 2-adicity or the group FFT's 2^26, npoly outside 0..n,
+ * a null buffer, overlapping buffers, a device error.  Synchronous, on the calling thread's device. */
+ZKG_API size_t zkg_kzg_open_all_table_bytes(int curve, int log_n, int log_l);
+ZKG_API int zkg_kzg_open_all_table_device(int curve, int log_n, int log_l, const uint64_t *d_srs_affine,
+                                          uint64_t *d_table);
+ZKG_API int zkg_kzg_open_all_device(int curve, int log_n, int log_l, int npoly, const uint64_t *d_poly,
+                                    const uint64_t *d_table, int affine_out, uint64_t *d_proofs);
+
 /* timing probe of the dominant kernel (MSM bucket accumulation / NTT pass chain),
  * measured with HIP events on each device's own stream; read sums over devices */
 ZKG_API void zkg_timer_enable(int on);

@@ -285,6 +285,64 @@ ZKG_API int zkg_kzg_open_device(int curve, int n, const uint64_t *d_poly, const 
   });
 }
 
+}  // extern "C"
+
+// ---------------------------------------------------------------------------- all openings (FK20)
+// every proof of a domain, single points or cosets of size l, from one Toeplitz product (zk_fk20.hip)
+#include "zk_fk20.hpp"
+
+namespace {
+bool kzg_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+// the shape rules every open_all entry shares: 0 when (curve, log_n, log_l) is one the library runs
+int open_all_shape(int curve, int log_n, int log_l) {
+  if (curve != ZKG_BN128 && curve != ZKG_BLS12_381) return kzg_refuse("kzg_open_all: unknown curve");
+  if (log_n < 1 || log_n > 28) return kzg_refuse("kzg_open_all: log_n out of range (1..28)");
+  if (log_l < 0 || log_l > log_n - 1) return kzg_refuse("kzg_open_all: the coset size must leave r = n / l >= 2");
+  const int two_adicity = curve == ZKG_BN128 ? ZK_BN128_FFT_LOG : ZK_BLS12_381_FFT_LOG;
+  if (log_n - log_l + 1 > two_adicity) return kzg_refuse("kzg_open_all: the 2r domain exceeds the field's 2-adicity");
+  if (log_n - log_l + 1 > 26) return kzg_refuse("kzg_open_all: the 2r domain exceeds the group FFT (2^26)");
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+ZKG_API size_t zkg_kzg_open_all_table_bytes(int curve, int log_n, int log_l) {
+  return open_all_shape(curve, log_n, log_l) ? 0 : zk::kzg_open_all_table_bytes(curve, log_n, log_l);
+}
+
+ZKG_API int zkg_kzg_open_all_table_device(int curve, int log_n, int log_l, const uint64_t *d_srs_affine,
+                                          uint64_t *d_table) {
+  if (open_all_shape(curve, log_n, log_l)) return -1;
+  if (!d_srs_affine || !d_table) return kzg_refuse("kzg_open_all_table: null buffer");
+  const size_t NP = curve == ZKG_BN128 ? 4 : 6, n = (size_t)1 << log_n;
+  if (kzg_overlap(d_srs_affine, n * 2 * NP * 8, d_table, 2 * n * 2 * NP * 8))
+    return kzg_refuse("kzg_open_all_table: the table overlaps the SRS rows");
+  return guard_ret<int>(-1, [&] {
+    zk::kzg_open_all_table(curve, log_n, log_l, d_srs_affine, d_table);
+    return 0;
+  });
+}
+
+ZKG_API int zkg_kzg_open_all_device(int curve, int log_n, int log_l, int npoly, const uint64_t *d_poly,
+                                    const uint64_t *d_table, int affine_out, uint64_t *d_proofs) {
+  if (open_all_shape(curve, log_n, log_l)) return -1;
+  const size_t NP = curve == ZKG_BN128 ? 4 : 6, n = (size_t)1 << log_n, r = n >> log_l;
+  if (npoly < 0 || (size_t)npoly > n) return kzg_refuse("kzg_open_all: the polynomial is longer than the domain");
+  if (!d_table || !d_proofs || (npoly > 0 && !d_poly)) return kzg_refuse("kzg_open_all: null buffer");
+  const size_t pb = (size_t)npoly * 32, tb = 2 * n * 2 * NP * 8, ob = r * (affine_out ? 2 : 3) * NP * 8;
+  if (kzg_overlap(d_proofs, ob, d_poly, pb) || kzg_overlap(d_proofs, ob, d_table, tb) ||
+      kzg_overlap(d_poly, pb, d_table, tb))
+    return kzg_refuse("kzg_open_all: overlapping buffers");
+  return guard_ret<int>(-1, [&] {
+    zk::kzg_open_all(curve, log_n, log_l, npoly, d_poly, d_table, affine_out != 0, d_proofs);
+    return 0;
+  });
+}
+
 ZKG_API void zkg_ntt_device(int curve, int inverse, int m, const uint64_t *gen, const uint64_t *d_src,
                             uint64_t *d_tgt) {
   guard([&] { zk::ntt(curve, m, gen, d_src, d_tgt, false, inverse != 0); });

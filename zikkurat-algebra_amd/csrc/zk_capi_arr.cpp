@@ -406,6 +406,44 @@ ZKG_API size_t zkg_g1_scl_table_bytes(int curve, int c) {
   return curve == ZKG_BN128 || curve == ZKG_BLS12_381 ? zk::g1_scl_table_bytes(curve, c) : 0;
 }
 
+}  // extern "C"
+
+// the row-wise sum of scalar multiples (zk_fk20.hip)
+#include "zk_fk20.hpp"
+
+namespace {
+bool ranges_overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return abytes && bbytes && a0 < b0 + bbytes && b0 < a0 + abytes;
+}
+int rows_sum_g(int curve, int rows, int terms, const uint64_t *expos, int expos_mont, const uint64_t *bases,
+               int affine_out, uint64_t *tgt, bool host_io) {
+  if (curve != ZKG_BN128 && curve != ZKG_BLS12_381) return refuse("g1_scl_rows_sum: unknown curve");
+  if (rows < 0 || terms < 0) return refuse("g1_scl_rows_sum: negative size");
+  const size_t E = (size_t)rows * (size_t)terms, NP = curve == ZKG_BN128 ? 4 : 6;
+  if (E > (size_t)0x7fffffff) return refuse("g1_scl_rows_sum: rows x terms does not fit 31 bits");
+  if (rows > 0 && (!tgt || (E > 0 && (!expos || !bases)))) return refuse("g1_scl_rows_sum: null buffer");
+  const size_t out_bytes = (size_t)rows * (affine_out ? 2 : 3) * NP * 8;
+  if (ranges_overlap(tgt, out_bytes, expos, E * 32) || ranges_overlap(tgt, out_bytes, bases, E * 2 * NP * 8))
+    return refuse("g1_scl_rows_sum: the target overlaps an input");
+  return guard_ret<int>(-1, [&] {
+    zk::g1_scl_rows_sum(curve, rows, terms, expos, expos_mont != 0, bases, affine_out != 0, tgt, host_io);
+    return 0;
+  });
+}
+}  // namespace
+
+extern "C" {
+
+ZKG_API int zkg_g1_scl_rows_sum_device(int curve, int rows, int terms, const uint64_t *d_expos, int expos_mont,
+                                       const uint64_t *d_bases, int affine_out, uint64_t *d_tgt) {
+  return rows_sum_g(curve, rows, terms, d_expos, expos_mont, d_bases, affine_out, d_tgt, false);
+}
+ZKG_API int zkg_g1_scl_rows_sum(int curve, int rows, int terms, const uint64_t *expos, int expos_mont,
+                                const uint64_t *bases, int affine_out, uint64_t *tgt) {
+  return rows_sum_g(curve, rows, terms, expos, expos_mont, bases, affine_out, tgt, true);
+}
+
 // the same on G2: <C>_G2_proj_scl_Fr_mont / _scl_Fr_std (bls12_381_G2_proj.c:453-480) and normalize / to_affine
 ZKG_SCL_ENTRY(zkg_g2_scl_fixed_device, g2_scl_fixed, false)
 ZKG_SCL_ENTRY(zkg_g2_scl_fixed, g2_scl_fixed, true)

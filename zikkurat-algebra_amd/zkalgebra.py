@@ -101,6 +101,9 @@ EXTENSION_SYMBOLS += [f"zkg_g{g}_check_rows{d}" for g in (1, 2) for d in ("", "_
 # division by a linear factor, and the KZG prover on it
 EXTENSION_SYMBOLS += ["zkg_poly_div_linear_device", "zkg_poly_div_linear", "zkg_poly_set_lindiv_tile",
                       "zkg_poly_lindiv_tile", "zkg_kzg_commit_device", "zkg_kzg_open_device"]
+# row-wise sums of scalar multiples, and every KZG opening of a domain at once on them (FK20)
+EXTENSION_SYMBOLS += ["zkg_g1_scl_rows_sum_device", "zkg_g1_scl_rows_sum", "zkg_kzg_open_all_table_bytes",
+                      "zkg_kzg_open_all_table_device", "zkg_kzg_open_all_device"]
 PT_CANONICAL, PT_ON_CURVE, PT_IN_SUBGROUP, PT_INFINITY = 1, 2, 4, 8
 PT_VALID = PT_CANONICAL | PT_ON_CURVE | PT_IN_SUBGROUP
 COORDS_ID = {"affine": 0, "proj": 1, "jac": 2}
@@ -242,6 +245,14 @@ def load():
             lib.zkg_poly_set_lindiv_tile.restype = None
             lib.zkg_kzg_commit_device.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, vp]
             lib.zkg_kzg_open_device.argtypes = [ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, vp, vp]
+        if hasattr(lib, "zkg_kzg_open_all_device"):  # absent from an older variant build, as above
+            vp = ctypes.c_void_p
+            for f in (lib.zkg_g1_scl_rows_sum_device, lib.zkg_g1_scl_rows_sum):
+                f.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp]
+            lib.zkg_kzg_open_all_table_bytes.restype = ctypes.c_size_t
+            lib.zkg_kzg_open_all_table_bytes.argtypes = [ctypes.c_int] * 3
+            lib.zkg_kzg_open_all_table_device.argtypes = [ctypes.c_int] * 3 + [vp, vp]
+            lib.zkg_kzg_open_all_device.argtypes = [ctypes.c_int] * 4 + [vp, vp, ctypes.c_int, vp]
         lib.zkg_last_error.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
         lib.zkg_comm_unique_id.argtypes = [ctypes.c_void_p]
         lib.zkg_comm_init.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
@@ -1114,6 +1125,32 @@ def scalar_mul_rows_device(curve, n, d_scalars, d_bases, d_tgt, std=False, affin
                                          1 if affine else 0, d_tgt.ptr)
 
 
+def scalar_mul_rows_sum(curve, scalars, bases, std=False, affine=False):
+    """sum_j [k_(j,i)] P_(j,i) per row i: scalars (terms, rows, 4) and affine bases (terms, rows, 2 NP), term-major
+    (zkg_g1_scl_rows_sum) -> `rows` normalised projective rows, or affine; the fold of scalar_mul_rows with g1_add"""
+    scalars = np.ascontiguousarray(scalars, dtype=np.uint64)
+    bases = np.ascontiguousarray(bases, dtype=np.uint64)
+    if scalars.ndim != 3 or scalars.shape[2] != NLIMBS_R:
+        raise TypeError("scalar_mul_rows_sum: the scalars must have shape (terms, rows, 4)")
+    terms, rows = scalars.shape[:2]
+    if bases.shape != (terms, rows, 2 * NLIMBS_P[curve]):
+        raise ValueError("scalar_mul_rows_sum: incompatible array dimensions")
+    require_gpu()
+    out = _scl_out(curve, rows, affine)
+    _lindiv_rc(load().zkg_g1_scl_rows_sum(CURVE_ID[curve], rows, terms, scalars.ctypes.data, 0 if std else 1,
+                                          bases.ctypes.data, 1 if affine else 0, out.ctypes.data),
+               "scalar_mul_rows_sum")
+    return out
+
+
+def scalar_mul_rows_sum_device(curve, rows, terms, d_scalars, d_bases, d_tgt, std=False, affine=False):
+    """device-resident scalar_mul_rows_sum (zkg_g1_scl_rows_sum_device); returns the code, nonzero for a refused
+    call (last_error() has the text)"""
+    return load().zkg_g1_scl_rows_sum_device(CURVE_ID[curve], rows, terms, d_scalars.ptr if d_scalars else None,
+                                             0 if std else 1, d_bases.ptr if d_bases else None, 1 if affine else 0,
+                                             d_tgt.ptr if d_tgt else None)
+
+
 def srs_powers(curve, tau, n, base, a=None, affine=False):
     """[a tau^i] P, i < n: the `taus` of mkKZGSetup (examples/KZG.hs:59-62); tau, a Montgomery Fr (a None = 1)"""
     require_gpu()
@@ -1257,6 +1294,25 @@ class KZGSetup:
     g2_tau_g2: tuple
     tau_g2s: "DeviceBuffer" = None
     _affine: dict = None
+    _open_all: dict = None
+
+    def open_all_table(self, log_n, coset_log):
+        """the device table of kzg_open_all for (log_n, coset_log), built on first use (zkg_kzg_open_all_table_device)
+        and kept until free()"""
+        if self._open_all is None:
+            self._open_all = {}
+        key = (int(log_n), int(coset_log))
+        if key not in self._open_all:
+            cid = CURVE_ID[self.domain.curve]
+            buf = DeviceBuffer.empty(load().zkg_kzg_open_all_table_bytes(cid, *key))
+            try:
+                _lindiv_rc(load().zkg_kzg_open_all_table_device(cid, key[0], key[1], self.affine_rows("tau_g1s").ptr,
+                                                                buf.ptr), "kzg_open_all")
+            except Exception:
+                buf.free()
+                raise
+            self._open_all[key] = buf
+        return self._open_all[key]
 
     def affine_rows(self, which):
         """the device buffer of affine rows of `which` ('tau_g1s' or 'lagrange_taus'), made once"""
@@ -1278,9 +1334,10 @@ class KZGSetup:
         self.lagrange_taus.free()
         if self.tau_g2s is not None:
             self.tau_g2s.free()
-        for b in (self._affine or {}).values():
+        for b in list((self._affine or {}).values()) + list((self._open_all or {}).values()):
             b.free()
         self._affine = None
+        self._open_all = None
 
 
 def kzg_setup(curve, tau, log_size, g1, g2, g2_powers=0):
@@ -1439,6 +1496,61 @@ def kzg_open(setup, poly, z, affine=False):
     return z, vals[0], proofs[0]
 
 
+# ---------------------------------------------------------------------------- all openings (FK20)
+# zk_fk20.hip: the proofs of a whole domain from one Toeplitz product; DESIGN.md "All openings (FK20)"
+
+def fk20_coeff_index(r, p):
+    """row p < 2r of the circulant column c^(j) holds F^(j)_v, F^(j)_v = f_(l v + j); -1: zero (zk_fk20.hpp)"""
+    return r - 1 if p == 0 else (p - r - 1 if p >= r + 2 else -1)
+
+
+def fk20_srs_index(r, p):
+    """row p < 2r of x^(j) holds S^(j)_u, S^(j)_u = s_(l u + j); -1: the point at infinity (zk_fk20.hpp)"""
+    return r - 2 - p if p <= r - 2 else -1
+
+
+def _open_all_shape(setup, npoly, log_n, coset_log):
+    """(m, c) of a kzg_open_all call, or ValueError; no GPU call"""
+    m = setup.domain.log_size if log_n is None else int(log_n)
+    c = int(coset_log)
+    if m > setup.domain.log_size:
+        raise ValueError("kzg_open_all: the domain is larger than the KZG setup")
+    if m < 1:
+        raise ValueError("kzg_open_all: the domain has at least two points")
+    if npoly > 1 << m:
+        raise ValueError("kzg_open_all: the polynomial is longer than the domain")
+    if not 0 <= c <= m - 1:
+        raise ValueError("kzg_open_all: the coset size 2^coset_log must leave at least two cosets")
+    return m, c
+
+
+def kzg_open_all(setup, poly, log_n=None, coset_log=0, affine=False):
+    """every opening of the domain of size n = 2^log_n (default: the setup's) at once: (values (n, 4), proofs).
+    values = forward_ntt of the zero-extended polynomial, natural order.  With l = 2^coset_log and r = n / l,
+    proofs has r rows (normalised projective, or affine): row k commits to the quotient of poly by
+    x^l - omega^(l k) and opens the coset omega^k <omega^r>, the values k, k + r, ..; for l = 1 it is
+    kzg_open(setup, poly, omega^k).  The per-setup table is built on first use (KZGSetup.open_all_table)."""
+    poly = _fr(poly)
+    curve = setup.domain.curve
+    m, c = _open_all_shape(setup, poly.shape[0], log_n, coset_log)
+    require_gpu()
+    n, NP = 1 << m, NLIMBS_P[curve]
+    ext = np.zeros((n, 4), dtype=np.uint64)
+    ext[:poly.shape[0]] = poly
+    values = forward_ntt(get_fft_subgroup(curve, m), ext)
+    table = setup.open_all_table(m, c)
+    proofs = np.zeros((n >> c, (2 if affine else 3) * NP), dtype=np.uint64)
+    d_p, d_out = DeviceBuffer(poly), DeviceBuffer.empty(proofs.nbytes)
+    try:
+        _lindiv_rc(load().zkg_kzg_open_all_device(CURVE_ID[curve], m, c, poly.shape[0], d_p.ptr if poly.shape[0] else None,
+                                                  table.ptr, 1 if affine else 0, d_out.ptr), "kzg_open_all")
+        proofs = d_out.to_host(proofs)
+    finally:
+        d_p.free()
+        d_out.free()
+    return values, proofs
+
+
 # ---------------------------------------------------------------------------- pairings
 # <C>_pairing_affine / _projective / _final_expo (lib/cbits/curves/pairing); Pairing.hs `pairing`
 
@@ -1576,6 +1688,42 @@ def kzg_verify(curve, g1, g2, tau_g2, commitment, x0, y0, proof, validate=False)
     point = g1_add(curve, g1_add(curve, commitment, xq), _g1_neg_proj(curve, yg))
     neg_aff = g1_to_affine(curve, _g1_neg_proj(curve, point))
     return pairing_check(curve, np.stack([proof_aff, neg_aff]), np.stack([tau_g2, g2]))
+
+
+def kzg_verify_coset(curve, g1, g2, tau_l_g2, commitment, shift, values_l, proof):
+    """the multi-reveal check of one kzg_open_all proof with l = len(values_l) = 2^c: values_l[i] =
+    f(shift gen_l^i), gen_l the generator of get_fft_subgroup(curve, c) (row k of the proofs: shift = omega^k,
+    values_l = values[k::r]).  With I the interpolation of the values on the coset (coset_intt) it holds when
+    pairing(proof, [tau^l] g2 - [shift^l] g2) == pairing(commitment - [I(tau)] g1, g2).  Composition only:
+    g1: the affine G1 rows [tau^i] g1, i < l (at least l of them; row 0 is the generator), for the commitment to I;
+    g2, tau_l_g2 = [tau^l] g2: affine G2 (kzg_setup(.., g2_powers > l) has the latter); commitment and proof
+    projective G1 rows; shift Montgomery Fr."""
+    NP = NLIMBS_P[curve]
+    values_l = _fr(values_l)
+    l = values_l.shape[0]
+    c = l.bit_length() - 1
+    g1 = np.ascontiguousarray(g1, dtype=np.uint64)
+    g2 = np.ascontiguousarray(g2, dtype=np.uint64).reshape(-1)
+    tau_l_g2 = np.ascontiguousarray(tau_l_g2, dtype=np.uint64).reshape(-1)
+    commitment = np.ascontiguousarray(commitment, dtype=np.uint64).reshape(-1)
+    proof = np.ascontiguousarray(proof, dtype=np.uint64).reshape(-1)
+    if l < 1 or l != 1 << c:
+        raise ValueError("kzg_verify_coset: the number of values is a power of two")
+    if g1.ndim != 2 or g1.shape[1] != 2 * NP or g1.shape[0] < l:
+        raise ValueError("kzg_verify_coset: g1 must hold the affine rows [tau^i] g1, i < l")
+    if g2.shape[0] != 4 * NP or tau_l_g2.shape[0] != 4 * NP or commitment.shape[0] != 3 * NP or proof.shape[0] != 3 * NP:
+        raise ValueError("kzg_verify_coset: incompatible array dimensions")
+    shift = _k(shift)
+    require_gpu()
+    r = FR_ORDER[curve]
+    s = sum(int(shift[j]) << (64 * j) for j in range(4)) * pow(1 << 256, -1, r) % r
+    interp = coset_intt(get_fft_subgroup(curve, c), shift, values_l)
+    i_tau = msm(curve, interp, np.ascontiguousarray(g1[:l]))
+    point = g1_add(curve, commitment, _g1_neg_proj(curve, i_tau))
+    neg_aff = g1_to_affine(curve, _g1_neg_proj(curve, point))
+    coeffs = np.stack([_fr_mont(curve, 1), _fr_mont(curve, -pow(s, l, r))])
+    d = g2_msm(curve, coeffs, np.stack([tau_l_g2, g2]), affine=True)
+    return pairing_check(curve, np.stack([g1_to_affine(curve, proof), neg_aff]), np.stack([d, g2]))
 
 
 # ---------------------------------------------------------------------------- point validation
